@@ -12,9 +12,15 @@ N rank processes itself; launch_mode / spawn_ranks).
 Timing: W untimed steps, then K steps bracketed by barrier + synchronize, max
 over ranks.  Rank 0 prints one JSON line.
 
-Extra fields: per-stage HIP-event times and rooflines, single-square latency
-(k=128, config 2), k=512 single square (config 3, GF(2^16)), and the CPU
-baseline (oracle/cda_oracle.c "port", same rsmt2d structure, host threads).
+A plain run does only that: set-up, W warm-up steps, the K timed steps,
+`--dump-outputs DIR` if asked (the last step's outputs as .npy files, see
+dump_outputs), the line (metric, value, ms_per_step, ...).
+
+With `--full` the run goes on as every run did before the option existed and
+the line carries the extra fields: the data roots checked against the oracle
+fixtures, per-stage HIP-event times and rooflines, single-square latency
+(k=128, config 2), k=512 single square (config 3, GF(2^16)), config 5, and the
+CPU baseline (oracle/cda_oracle.c "port", same rsmt2d structure, host threads).
 """
 from __future__ import annotations
 
@@ -860,6 +866,50 @@ def gather_parity(parity: dict, world: int, device) -> dict:
     return {"checked": sum(c for c, _ in per), "matched": sum(m for _, m in per), "per_rank": per}
 
 
+DUMP_SEED = 20240531
+DUMP_ROOT_SQUARES = 64      # squares whose 2 x 2k axis roots are written
+DUMP_EDS_SHARES = 4096      # EDS shares written (512 B each)
+
+
+def dump_outputs(path: str, k: int, batch: int, d_eds, d_rows, d_cols, d_roots, d_status) -> dict:
+    """--dump-outputs: what the timed path left in the caller's device buffers
+    after its last step, as .npy files (bytes as float32, where every byte
+    value is exact; status and the indexes as float64), so two builds can be
+    compared output for output:
+      data_roots  [batch, 32]      every square's data root (it covers the
+                                   square's whole EDS and all its axis roots)
+      status      [batch]          every square's push-order status
+      row_roots   [n, 2k, 90]      row roots of a sample of n squares
+      col_roots   [n, 2k, 90]      column roots of the same squares
+      eds_shares  [m, 512]         a sample of m EDS shares
+      *_index                      which squares / (square, row, col) cells
+    The samples come from a fixed seed and depend only on (k, batch); the
+    files hold about 20 MB at the default shape.  Gathered on the device: the
+    EDS arena itself (32 GiB at 1 024 squares) never crosses to the host."""
+    import numpy as np
+    import torch
+
+    W = 2 * k
+    rng = np.random.default_rng(DUMP_SEED)
+    sq = np.sort(rng.choice(batch, size=min(batch, DUMP_ROOT_SQUARES), replace=False)).astype(np.int64)
+    cell = np.sort(rng.integers(0, batch * W * W, size=DUMP_EDS_SHARES, dtype=np.int64))
+    dev = d_eds.device
+    out = {
+        "data_roots": d_roots.view(batch, 32),
+        "status": d_status.view(batch),
+        "row_roots": d_rows.view(batch, W, 90)[torch.from_numpy(sq).to(dev)],
+        "col_roots": d_cols.view(batch, W, 90)[torch.from_numpy(sq).to(dev)],
+        "eds_shares": d_eds.view(batch * W * W, SHARE)[torch.from_numpy(cell).to(dev)],
+    }
+    out = {name: t.cpu().numpy().astype(np.float64 if name == "status" else np.float32) for name, t in out.items()}
+    out["roots_index"] = sq.astype(np.float64)
+    out["eds_shares_index"] = np.stack([cell // (W * W), cell // W % W, cell % W], axis=1).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return out
+
+
 def launch_mode(gpus: int, env) -> str:
     """How `bench.py --gpus N` runs:
     - WORLD_SIZE set (torch.distributed.run or our own spawn): this process is
@@ -979,7 +1029,20 @@ def main():
                     help="inplace: ODS already in Q0 of the EDS arena (cda_extend_dah_inplace_device, the layout "
                          "rsmt2d's EDS has; no Q0 copy); packed: ODS in its own k*k buffer "
                          "(cda_extend_dah_device, Q0 copied into the EDS)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else: the oracle-fixture check of the data roots, "
+                         "the per-stage pass and rooflines, the extras (latency, other layout, host buffers, "
+                         "construction, commitments, proofs, repair, k=512, config 5) and the CPU baseline; "
+                         "--no-cpu / --no-extras / --config5 narrow or widen a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left in the caller's buffers as "
+                         "DIR/<name>.npy (float32 / float64): data_roots and status whole, row_roots, col_roots and "
+                         "eds_shares as a fixed seeded sample (dump_outputs); at N > 1 rank 0 writes its shard")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.config5 and not args.full:
+        ap.error("--config5 is one of the extras: it needs --full")
 
     mode = launch_mode(args.gpus, os.environ) if not args.config5_child else "rank"
     if mode == "mismatch":
@@ -993,7 +1056,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     cfg5 = None
-    if (world > 1 or args.config5) and not args.no_extras and not args.config5_child:
+    if args.full and (world > 1 or args.config5) and not args.no_extras and not args.config5_child:
         # config 5: ONE k=512 square split by row blocks over all ranks (RCCL
         # all-to-all of the row-encoded blocks, column encode + hashing per
         # rank, gather of subtree/column roots, combine on rank 0), run by a
@@ -1084,7 +1147,8 @@ def main():
         step()
     torch.cuda.synchronize(dev)
     parity = {"checked": 0, "matched": 0}
-    if not os.environ.get("CDA_BENCH_NOCHECK"):   # set only for timing-diagnostic library variants
+    # --full only; CDA_BENCH_NOCHECK is set only for timing-diagnostic library variants
+    if args.full and not os.environ.get("CDA_BENCH_NOCHECK"):
         assert int(d_status.abs().sum().item()) == 0, "push-order status set on ordered input"
         roots = d_roots.view(B, 32).cpu().numpy()
         if nd < B:   # tiled inputs must give tiled data roots
@@ -1104,13 +1168,55 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    if world > 1:   # every rank's shard is checked against the fixture; the line reports all of them
+    if world > 1 and args.full:   # every rank's shard is checked against the fixture; the line reports all of them
         parity = gather_parity(parity, world, dev if dist.get_backend() == "nccl" else "cpu")
 
     # the timed region runs the product path exactly as a caller would (no
     # stage events); the per-stage HIP-event breakdown comes from a separate
     # pass afterwards (the events add ~10 us launch gaps at stage borders)
     el = time_region(step, args.steps, lambda: torch.cuda.synchronize(dev), world, reduce_max, dist.barrier)
+    value = B * world * args.steps / el
+
+    def headline():
+        return {
+            "metric": "EDS+DAH squares/sec (k=128)",
+            "value": value,
+            "unit": "squares/s",
+            "n_gpus": world,
+            "launch": launch,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": 1e3 * el / args.steps,
+            "higher_is_better": True,
+            "scaling": "strong" if B * world == CONFIG4_SQUARES else "weak",
+            "vs_baseline": None,
+            "dtype": "u8/u32",
+            "data": (f"synthetic random-namespace squares (testfactory mirror, SplitMix64), "
+                     f"{'all distinct' if nd == B else f'{nd} distinct tiled'}: square indexes "
+                     f"{idx[0]}..{idx[-1]} on rank 0 (generated on host threads in {t_gen:.1f} s, "
+                     f"HBM-resident before timing)"),
+            "config": {"workload": (f"config 4: {B * world} independent k={k} squares per step split over "
+                                    f"{world} GPU(s), {B} per GPU (rank g: squares [{B}g, {B}g+{B}))"
+                                    if B * world == CONFIG4_SQUARES else
+                                    f"{B} independent k={k} squares per GPU per step (not config 4's fixed "
+                                    f"1024-square workload)"),
+                       "k": k, "squares_per_step": B * world, "squares_per_gpu_per_step": B,
+                       "distinct_squares": nd, "parallelism": f"dp{world} (independent squares)",
+                       "layout": args.layout},
+            "ods_gb_per_s": value * k * k * SHARE / 1e9,
+            "full": args.full,
+        }
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, k, B, d_eds, d_rows, d_cols, d_roots, d_status)
+    if not args.full:
+        # a plain run ends here: set-up, warm-up, the timed steps, the line
+        if rank == 0:
+            print(json.dumps(headline()))
+        if dist.is_initialized():
+            dist.destroy_process_group()
+        return
+
     ctx.set_profiling(True)
     ctx.stage_times()
     n_prof = max(3, min(args.steps, 10))
@@ -1118,8 +1224,6 @@ def main():
     ctx.set_profiling(False)
     st = ctx.stage_times()
 
-    total_sq = B * world * args.steps
-    value = total_sq / el
     stages = stage_report(st, k, B, args.layout == "inplace", n_prof)
     dom = max((s for s in stages if "achieved" in stages[s]), key=lambda s: stages[s]["avg_ms"])
     d = stages[dom]
@@ -1334,32 +1438,8 @@ def main():
 
     def make_line(cpu):
         return {
-            "metric": "EDS+DAH squares/sec (k=128)",
-            "value": value,
-            "unit": "squares/s",
-            "n_gpus": world,
-            "launch": launch,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * el / args.steps,
-            "higher_is_better": True,
-            "scaling": "strong" if B * world == CONFIG4_SQUARES else "weak",
-            "vs_baseline": None,
-            "dtype": "u8/u32",
-            "data": (f"synthetic random-namespace squares (testfactory mirror, SplitMix64), "
-                     f"{'all distinct' if nd == B else f'{nd} distinct tiled'}: square indexes "
-                     f"{idx[0]}..{idx[-1]} on rank 0 (generated on host threads in {t_gen:.1f} s, "
-                     f"HBM-resident before timing)"),
-            "config": {"workload": (f"config 4: {B * world} independent k={k} squares per step split over "
-                                    f"{world} GPU(s), {B} per GPU (rank g: squares [{B}g, {B}g+{B}))"
-                                    if B * world == CONFIG4_SQUARES else
-                                    f"{B} independent k={k} squares per GPU per step (not config 4's fixed "
-                                    f"1024-square workload)"),
-                       "k": k, "squares_per_step": B * world, "squares_per_gpu_per_step": B,
-                       "distinct_squares": nd, "parallelism": f"dp{world} (independent squares)",
-                       "layout": args.layout},
+            **headline(),
             "parity": {**parity, "fixture": "tests/golden/config4_k128{,_rest}.json (oracle data roots of squares 0..1023)"},
-            "ods_gb_per_s": value * k * k * SHARE / 1e9,
             "stage_pass": {"steps": n_prof, "ms_per_step": 1e3 * el_prof / n_prof,
                            "note": "stages and rooflines come from this separate pass with HIP events at every "
                                    "stage border, on the one-stream schedule; value / ms_per_step come from the "

@@ -1,5 +1,6 @@
 """CPU tests of the oracle (the checker): pinned against the reference's own
 golden vectors and fixtures before anything is compared with the GPU."""
+import base64
 import gzip
 import hashlib
 import json
@@ -14,7 +15,6 @@ import square
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = json.load(open(os.path.join(HERE, "golden", "golden.json")))
-REF_BLOCK = "/root/reference/x/blob/test/testdata/block_response.json"
 
 
 def block408_ods():
@@ -51,9 +51,17 @@ def test_block408_data_root():
     assert hashlib.sha256(eds.tobytes()).hexdigest() == g["eds_sha256"]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BLOCK), reason="reference tree not present")
+def block408():
+    """The block's txs, square size and header.data_hash: the data of the
+    reference fixture x/blob/test/testdata/block_response.json, stored by
+    oracle/gen_golden.py."""
+    with gzip.open(os.path.join(HERE, "golden", "block408_txs.json.gz"), "rt") as f:
+        d = json.load(f)
+    return [base64.b64decode(t) for t in d["txs"]], d["square_size"], bytes.fromhex(d["data_hash"])
+
+
 def test_square_construction_reproduces_fixture():
-    txs, k, data_hash = square.load_block(REF_BLOCK)
+    txs, k, data_hash = block408()
     ods = np.frombuffer(b"".join(square.construct(txs, k)), dtype=np.uint8).reshape(-1, 512)
     assert np.array_equal(ods, block408_ods())
     assert data_hash.hex() == GOLDEN["block408"]["data_hash"]

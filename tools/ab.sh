@@ -16,7 +16,7 @@ for r in $(seq 1 "$rounds"); do
   i=0
   for v in "$@"; do
     f="$out/${i}_${r}.json"
-    if ! env $v timeout -k 10 300 python3 bench.py $args > "$f" 2> "$out/${i}_${r}.err"; then
+    if ! env $v timeout -k 10 300 python3 bench.py --full $args > "$f" 2> "$out/${i}_${r}.err"; then
       echo "variant $i round $r failed: $v" | tee -a "$out/ab.txt"
       exit 1
     fi

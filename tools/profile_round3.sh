@@ -18,9 +18,9 @@ for K in ${KS:-128 512}; do
   OUT=$R/gpurun_out/prof_${TAG}_k$K
   rm -rf $OUT; mkdir -p $OUT
   if [ $K = 128 ]; then
-    B="$R/bench.py --no-cpu --no-extras --steps 3 --warmup 1"; STEPS=7; SQ=1024
+    B="$R/bench.py --full --no-cpu --no-extras --steps 3 --warmup 1"; STEPS=7; SQ=1024
   else
-    B="$R/bench.py --k 512 --batch 1 --distinct 1 --no-cpu --no-extras --steps 4 --warmup 1"; STEPS=9; SQ=1
+    B="$R/bench.py --full --k 512 --batch 1 --distinct 1 --no-cpu --no-extras --steps 4 --warmup 1"; STEPS=9; SQ=1
   fi
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python3 $B > $OUT/trace.log 2>&1 || exit 1
   timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- python3 $B > $OUT/fetch.log 2>&1 || exit 2

@@ -12,9 +12,9 @@ OUT=gpurun_out/n$N
 mkdir -p $OUT
 export CDA_BENCH_DEVICE=0 CDA_BENCH_BACKEND=gloo CDA_CONFIG5_TIMEOUT_S=150
 timeout -k 10 560 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-  --master-port 29611 bench.py --gpus $N --steps 3 --warmup 1 > $OUT/launcher.log 2> $OUT/launcher.err \
+  --master-port 29611 bench.py --full --gpus $N --steps 3 --warmup 1 > $OUT/launcher.log 2> $OUT/launcher.err \
   || exit $?
-timeout -k 10 560 python bench.py --gpus $N --steps 3 --warmup 1 > $OUT/spawn.log 2> $OUT/spawn.err \
+timeout -k 10 560 python bench.py --full --gpus $N --steps 3 --warmup 1 > $OUT/spawn.log 2> $OUT/spawn.err \
   || exit $?
 python - "$OUT" <<'PY'
 import json, sys

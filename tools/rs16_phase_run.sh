@@ -5,7 +5,7 @@ set -e
 mkdir -p gpurun_out
 for v in base rs16_probe1 rs16_probe2; do
   if [ $v = base ]; then L=celestia-app_amd/libcda.so; else L=tools/var/$v/libcda.so; fi
-  CDA_LIB=$PWD/$L CDA_BENCH_NOCHECK=1 timeout -k 10 150 python bench.py --k 512 --batch 4 --no-cpu --no-extras \
+  CDA_LIB=$PWD/$L CDA_BENCH_NOCHECK=1 timeout -k 10 150 python bench.py --full --k 512 --batch 4 --no-cpu --no-extras \
     --steps 10 > gpurun_out/phase16_$v.log 2>&1
   python - "$v" <<'PY'
 import json, sys

@@ -12,4 +12,4 @@ ARGS=(tests -m gpu -x -v --timeout 300 --timeout-method thread)
 timeout -k 10 900 python -u -m pytest "${ARGS[@]}" > "$OUT/gpu_tests.log" 2>&1 || exit $?
 [ -n "$K" ] && exit 0
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || exit $?
-timeout -k 10 600 python -u bench.py > "$OUT/bench.log" 2>&1
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.log" 2>&1
