@@ -68,6 +68,7 @@ EXPORTED = (
     "cda_nmt_axis_roots", "cda_nmt_axis_root", "cda_nmt_prove_range", "cda_merkle_root",
     "cda_comm_unique_id", "cda_comm_init", "cda_comm_destroy", "cda_comm_size", "cda_comm_abort", "cda_extend_dah_split", "cda_split_rows_send",
     "cda_extend_dah_multi", "cda_split_layout", "cda_split_offsets", "cda_extend_dah_batch_ex",
+    "cda_share_proofs_verify",
 )
 STAGES = ("rs_q0", "rs_q3", "order_check", "nmt_leaves", "nmt_levels", "data_root")
 
@@ -105,6 +106,24 @@ class SplitLayoutT(C.Structure):
                [(n, C.c_uint64) for n in ("piece_bytes", "send_bytes", "col_block_bytes", "col_slots_off",
                                           "row_sub_off", "gather_sub_off", "gather_col_off", "err_off",
                                           "slots_bytes")]
+
+
+VERIFY_MAX_NS = 64         # CDA_VERIFY_MAX_NS
+VERIFY_MAX_LEAVES = 2048   # CDA_VERIFY_MAX_LEAVES
+
+
+class ShareProofBatch(C.Structure):
+    """cda_share_proof_batch (include/cda.h)."""
+    _u8p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    _i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    _fields_ = [("n_proofs", C.c_uint32), ("ns_len", C.c_uint32), ("share_len", C.c_uint32),
+                ("data_roots", _u8p), ("namespaces", _u8p), ("seg_off", _u32p),
+                ("nmt_start", _i32p), ("nmt_end", _i32p),
+                ("node_off", _u32p), ("nodes", _u8p), ("n_nodes", C.c_uint32),
+                ("row_roots", _u8p),
+                ("rfc_total", _i64p), ("rfc_index", _i64p), ("rfc_leaf_hash", _u8p),
+                ("aunt_off", _u32p), ("aunts", _u8p), ("n_aunts", C.c_uint32),
+                ("shares", _u8p), ("n_shares", C.c_uint64)]
 
 
 _lib = None
@@ -187,6 +206,7 @@ def load(path: str | None = None):
         L.cda_nmt_prove_range.argtypes = [ctxp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                           C.c_uint32, u8p, u32p, u8p]
         L.cda_merkle_root.argtypes = [ctxp, u8p, u64p, C.c_uint32, u8p]
+        L.cda_share_proofs_verify.argtypes = [ctxp, C.POINTER(ShareProofBatch), u8p]
         L.cda_comm_unique_id.argtypes = [u8p]
         L.cda_comm_init.argtypes = [ctxp, C.c_int, C.c_int, u8p]
         L.cda_comm_destroy.argtypes = [ctxp]

@@ -34,12 +34,45 @@ class Proof:                        # go-square/merkle Proof (RowProof.Proofs)
     aunts: list
 
 
+ERR_ROW_PROOF = "row proof failed to verify"        # row_proof.go:22
+ERR_SHARE_PROOF = "share proof failed to verify"    # share_proof.go:48
+
+
 @dataclass
 class RowProof:
     row_roots: list
     proofs: list
     start_row: int
     end_row: int
+
+    def structural_error(self):
+        """RowProof.Validate's count checks (row_proof.go:15-20): the error
+        text, or None.  No GPU."""
+        rows = self.end_row - self.start_row + 1
+        if rows != len(self.row_roots):
+            return f"the number of rows {rows} must equal the number of row roots {len(self.row_roots)}"
+        if len(self.proofs) != len(self.row_roots):
+            return f"the number of proofs {len(self.proofs)} must equal the number of row roots {len(self.row_roots)}"
+        return None
+
+    def validate(self, root: bytes, ctx=None):
+        """RowProof.Validate(root) (row_proof.go:13-27): None, or ValueError
+        with the reference's text.  The merkle proofs are verified on the GPU
+        (cda_share_proofs_verify, row half only)."""
+        err = self.structural_error()
+        if err is None and self.row_roots:
+            n = len(self.row_roots[0])
+            # (a namespace longer than the library's bound is the call's CDA_ERR_INVALID, not a verdict)
+            ok = n >= 34 and (n - 32) % 2 == 0 and len(root) == 32 \
+                and all(len(r) == n for r in self.row_roots) and all(_proof_well_formed(q) for q in self.proofs)
+            if ok:
+                segs = [(0, 1, [], r, q) for r, q in zip(self.row_roots, self.proofs)]
+                ok = _verify_batch(ctx, (n - 32) // 2, 0, [(bytes((n - 32) // 2), bytes(root), segs, [])],
+                                   rows=True, nmt=False)[0] == 0
+            if not ok:
+                err = ERR_ROW_PROOF
+        if err is not None:
+            raise ValueError(err)
 
 
 @dataclass
@@ -50,6 +83,52 @@ class ShareProof:
     row_proof: RowProof
     namespace_version: int = 0
     extra: dict = field(default_factory=dict)
+
+    def structural_error(self):
+        """The checks of ShareProof.Validate that come before the row proof
+        (share_proof.go:17-41) followed by RowProof.Validate's count checks,
+        in the reference's order: the error text, or None.  No GPU."""
+        if not self.data:
+            return "empty share proof"
+        n_in_proofs = sum(p.end - p.start for p in self.share_proofs)
+        rp = self.row_proof
+        if len(self.share_proofs) != len(rp.row_roots):
+            return (f"the number of share proofs {len(self.share_proofs)} must equal the number of row roots "
+                    f"{len(rp.row_roots)}")
+        if len(self.data) != n_in_proofs:
+            return (f"the number of shares {len(self.data)} must equal the number of shares in share proofs "
+                    f"{n_in_proofs}")
+        for p in self.share_proofs:
+            if p.start < 0:
+                return "proof index cannot be negative"
+            if p.end - p.start <= 0:
+                return "proof total must be positive"
+        return rp.structural_error()
+
+    def validate(self, root: bytes, ctx=None):
+        """ShareProof.Validate(root) (share_proof.go:16-52): None, or
+        ValueError with the reference's text, in the reference's order of
+        checks.  The structural checks need no GPU; the row proofs and the NMT
+        inclusion proofs are verified on it in one cda_share_proofs_verify call."""
+        err = validate_share_proofs([self], [root], ctx)[0]
+        if err is not None:
+            raise ValueError(err)
+
+    def verify_proof(self, ctx=None) -> bool:
+        """ShareProof.VerifyProof (share_proof.go:54-82): the NMT inclusion
+        proofs of the shares against the proof's own row roots (no data root)."""
+        if len(self.share_proofs) != len(self.row_proof.row_roots) or any(
+                p.start < 0 or p.end <= p.start for p in self.share_proofs) or len(self.data) != sum(
+                p.end - p.start for p in self.share_proofs):
+            return False
+        if not self.share_proofs:
+            return True
+        if not _nmt_well_formed(self):
+            return False
+        ns = bytes([self.namespace_version]) + bytes(self.namespace_id)
+        segs = [(p.start, p.end, p.nodes, r, None) for p, r in zip(self.share_proofs, self.row_proof.row_roots)]
+        return _verify_batch(ctx, len(ns), len(self.data[0]), [(ns, None, segs, self.data)],
+                             rows=False, nmt=True)[0] == 0
 
 
 def _log2(x: int) -> int:
@@ -149,6 +228,140 @@ class ResidentSquare:
         out = np.empty(90, dtype=np.uint8)
         self.ctx.check(self.ctx.lib.cda_square_subtree_root(self.h, row, ptr(w), len(walk), ptr(out)))
         return out.tobytes()
+
+
+# ------------------------------------------------------------ verification
+def _proof_well_formed(q) -> bool:
+    """A merkle Proof the batch call can carry: 32-byte hashes, int64 fields.
+    Anything else cannot verify (the hashes would differ in length)."""
+    return len(q.leaf_hash) == 32 and all(len(a) == 32 for a in q.aunts) and \
+        -(1 << 63) <= q.total < (1 << 63) and -(1 << 63) <= q.index < (1 << 63)
+
+
+def _row_well_formed(sp, root) -> bool:
+    n = 2 * (1 + len(sp.namespace_id)) + 32
+    return len(root) == 32 and all(len(r) == n for r in sp.row_proof.row_roots) and \
+        all(_proof_well_formed(q) for q in sp.row_proof.proofs)
+
+
+def _nmt_well_formed(sp) -> bool:
+    """The NMT half fits the batch layout: a one-byte namespace version, nodes
+    of 2*ns_len + 32 bytes, shares of one length.  Anything else fails
+    VerifyProof in the reference too.  (A namespace longer than the library's
+    bound is the call's CDA_ERR_INVALID, not a verdict.)"""
+    n = 2 * (1 + len(sp.namespace_id)) + 32
+    return 0 <= sp.namespace_version <= 255 and \
+        all(len(x) == n for p in sp.share_proofs for x in p.nodes) and \
+        all(len(r) == n for r in sp.row_proof.row_roots) and len({len(s) for s in sp.data}) == 1
+
+
+def _bytes_array(parts) -> np.ndarray:
+    a = np.frombuffer(b"".join(bytes(p) for p in parts), dtype=np.uint8)
+    return a if a.size else np.zeros(1, dtype=np.uint8)
+
+
+def _build_batch(ns_len: int, share_len: int, entries, rows: bool, nmt: bool):
+    """The cda_share_proof_batch of `entries`: (namespace, data root or None,
+    segments, shares) per proof, segments: (start, end, nodes, row root,
+    merkle Proof or None) per row.  Returns (struct, arrays it points into)."""
+    segs = [s for e in entries for s in e[2]]
+    u8p, u32p, i32p, i64p = (C.POINTER(t) for t in (C.c_uint8, C.c_uint32, C.c_int32, C.c_int64))
+    keep = []
+
+    def arr(a, t):
+        keep.append(a)
+        return a.ctypes.data_as(t)
+
+    def offsets(counts):
+        return np.cumsum([0] + list(counts), dtype=np.int64).astype(np.uint32)
+
+    b = _lib.ShareProofBatch()
+    b.n_proofs, b.ns_len, b.share_len = len(entries), ns_len, share_len
+    b.namespaces = arr(_bytes_array(e[0] for e in entries), u8p)
+    b.seg_off = arr(offsets(len(e[2]) for e in entries), u32p)
+    b.row_roots = arr(_bytes_array(s[3] for s in segs), u8p)
+    if rows:
+        b.data_roots = arr(_bytes_array(e[1] for e in entries), u8p)
+        b.rfc_total = arr(np.array([s[4].total for s in segs] or [0], dtype=np.int64), i64p)
+        b.rfc_index = arr(np.array([s[4].index for s in segs] or [0], dtype=np.int64), i64p)
+        b.rfc_leaf_hash = arr(_bytes_array(s[4].leaf_hash for s in segs), u8p)
+        b.aunt_off = arr(offsets(len(s[4].aunts) for s in segs), u32p)
+        b.aunts = arr(_bytes_array(a for s in segs for a in s[4].aunts), u8p)
+        b.n_aunts = sum(len(s[4].aunts) for s in segs)
+    if nmt:
+        b.nmt_start = arr(np.array([s[0] for s in segs] or [0], dtype=np.int32), i32p)
+        b.nmt_end = arr(np.array([s[1] for s in segs] or [0], dtype=np.int32), i32p)
+        b.node_off = arr(offsets(len(s[2]) for s in segs), u32p)
+        b.nodes = arr(_bytes_array(x for s in segs for x in s[2]), u8p)
+        b.n_nodes = sum(len(s[2]) for s in segs)
+        b.shares = arr(_bytes_array(x for e in entries for x in e[3]), u8p)
+        b.n_shares = sum(len(e[3]) for e in entries)
+    return b, keep
+
+
+def _verify_batch(ctx, ns_len: int, share_len: int, entries, rows: bool, nmt: bool) -> list:
+    """One cda_share_proofs_verify call over `entries` (_build_batch): the
+    verdict per proof (0 valid, 1 row proof, 2 share proof)."""
+    ctx = ctx or default_context()
+    b, keep = _build_batch(ns_len, share_len, entries, rows, nmt)
+    verdict = np.full(max(1, len(entries)), 255, dtype=np.uint8)
+    ctx.check(ctx.lib.cda_share_proofs_verify(ctx.h, C.byref(b), ptr(verdict)))
+    del keep
+    return [int(v) for v in verdict[:len(entries)]]
+
+
+def validate_share_proofs(proofs, roots, ctx=None) -> list:
+    """ShareProof.Validate(root) for many proofs at once: per proof None, or
+    the reference's error text.  Proofs that fail a structural check are
+    answered here and never reach the GPU; the rest go into one
+    cda_share_proofs_verify call per distinct namespace length (and share
+    length).  A field of the wrong length cannot verify in the reference
+    either (its hash, or the comparison, differs), so such a proof gets the
+    verdict Validate gives without being hashed: a malformed row root, leaf
+    hash, aunt or data root is "row proof failed to verify"; a malformed NMT
+    node, share or namespace version is "share proof failed to verify", and
+    only if the proof's row proofs verify (they run in a row-only call)."""
+    if len(proofs) != len(roots):
+        raise ValueError(f"{len(proofs)} proofs but {len(roots)} roots")
+    out = [None] * len(proofs)
+    full, row_only = {}, {}   # (ns_len, share_len) -> proof indexes
+    for i, (p, root) in enumerate(zip(proofs, roots)):
+        err = p.structural_error()
+        if err is not None:
+            out[i] = err
+        elif not _row_well_formed(p, root):
+            out[i] = ERR_ROW_PROOF
+        elif not _nmt_well_formed(p):
+            row_only.setdefault((1 + len(p.namespace_id), 0), []).append(i)
+        else:
+            full.setdefault((1 + len(p.namespace_id), len(p.data[0])), []).append(i)
+    for groups, nmt in ((full, True), (row_only, False)):
+        for (ns_len, share_len), idx in groups.items():
+            entries = []
+            for i in idx:
+                p = proofs[i]
+                ns = bytes([p.namespace_version & 0xFF]) + bytes(p.namespace_id)
+                segs = [(s.start, s.end, s.nodes if nmt else [], r, q)
+                        for s, r, q in zip(p.share_proofs, p.row_proof.row_roots, p.row_proof.proofs)]
+                entries.append((ns, bytes(roots[i]), segs, p.data if nmt else []))
+            for i, v in zip(idx, _verify_batch(ctx, ns_len, share_len, entries, rows=True, nmt=nmt)):
+                out[i] = ERR_ROW_PROOF if v == 1 else ERR_SHARE_PROOF if (v == 2 or not nmt) else None
+    return out
+
+
+def nmt_verify_inclusion(root: bytes, nodes, start: int, end: int, namespace: bytes, leaves, ctx=None) -> bool:
+    """nmt Proof.VerifyInclusion (IgnoreMaxNamespace proofs) of `leaves` as
+    leaves [start, end) under `namespace` (version || id) against `root`: the
+    NMT half of VerifyProof alone, pairing with cda_nmt_prove_range and
+    wrapper's ProveRange."""
+    n = 2 * len(namespace) + 32
+    leaves = [bytes(x) for x in leaves]
+    if start < 0 or end <= start or len(leaves) != end - start or len(root) != n or \
+            any(len(x) != n for x in nodes) or len({len(x) for x in leaves}) != 1:
+        return False
+    seg = (start, end, [bytes(x) for x in nodes], bytes(root), None)
+    return _verify_batch(ctx, len(namespace), len(leaves[0]), [(bytes(namespace), None, [seg], leaves)],
+                         rows=False, nmt=True)[0] == 0
 
 
 def _go_namespace(ns: bytes) -> str:

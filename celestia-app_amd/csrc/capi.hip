@@ -669,6 +669,10 @@ int cda_merkle_root(cda_ctx* ctx, const uint8_t* items, const uint64_t* off, uin
     });
 }
 
+int cda_share_proofs_verify(cda_ctx* ctx, const cda_share_proof_batch* b, uint8_t* verdict) {
+    return guarded(ctx, [&](cda::Engine& e) -> int { return e.share_proofs_verify(b, verdict); });
+}
+
 int cda_comm_unique_id(uint8_t* id) {
     if (!id) return CDA_ERR_INVALID;
     tl_err.msg.clear();

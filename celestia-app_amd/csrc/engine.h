@@ -14,6 +14,8 @@
 #include "cda_kernels.h"
 #include "square_plan.h"
 
+struct cda_share_proof_batch;   // include/cda.h
+
 namespace cda {
 
 // Page-locks a caller's host buffer for the duration of a call (RAII), so
@@ -282,6 +284,11 @@ class Engine {
                         uint8_t* root);
     int merkle_root(const uint8_t* items, const uint64_t* off, uint32_t n, uint8_t* out);
 
+    // Batched share / row proof verification (verify.hip): validates the
+    // batch on the host, then four launches on the context's stream and one
+    // synchronisation; verdict[p] = 0 valid, 1 row proof, 2 share proof.
+    int share_proofs_verify(const cda_share_proof_batch* b, uint8_t* verdict);
+
     // Stage timing with HIP events on the launch stream (bench / profiling).
     enum Stage { kStageRsQ0 = 0, kStageRsQ3, kStageOrder, kStageLeaves, kStageLevels, kStageDataRoot, kNumStages };
     void set_profiling(bool on) { profiling_ = on; }
@@ -413,6 +420,8 @@ class Engine {
     std::vector<uint8_t> rp_roots_;
     // standalone trees: host cells, all tree levels, axis indexes / error words, roots
     DevBuf tr_cells_, tr_levels_, tr_axis_, tr_roots_;
+    // proof verification: the uploaded batch; leaf / fold node scratch, flags and verdicts
+    DevBuf vp_in_, vp_scratch_;
     DevBuf rs_pad_;   // Codec.Encode of a non-power-of-two shard count
     // config 5 in the library: RCCL communicator (ncclComm_t), row block,
     // send buffer, column block, slots

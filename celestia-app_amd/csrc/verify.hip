@@ -1,0 +1,550 @@
+// verify.hip -- batched verification of share and row proofs.
+//
+// Reference behaviour (paths under the celestia-app v3 tree; EXT = module
+// pinned in go.mod):
+//   * pkg/proof/share_proof.go:16-82 ShareProof.Validate / VerifyProof and
+//     pkg/proof/row_proof.go:13-51 RowProof.Validate: the hashed halves (the
+//     structural checks stay with the caller);
+//   * nmt v0.22.0 (EXT) Proof.VerifyInclusion with IgnoreMaxNamespace(true):
+//     leaf = nid || nid || sha256(0x00 || nid || share), the subtree of
+//     pow2ceil(end) leaves from the range's leaves and the proof nodes, the
+//     remaining nodes folded in on the right, all N bytes compared;
+//   * go-square/merkle (EXT v1.1.0) Proof.Verify / computeHashFromAunts for any
+//     total (RFC-6962 split at the largest power of two below the total).
+//
+// Four launches per batch, whatever the mix of proofs:
+//   1. vp_leaf_kernel   one thread per share of the batch: the leaf node into
+//                       a scratch slot.  ns_len 29 with 512-B shares runs the
+//                       word-level leaf hashing of leaf_dev.h (nine blocks,
+//                       one v_perm per message word); any other size a
+//                       byte-addressed SHA-256.
+//   2. vp_fold_kernel   one wave per segment (one row's NMT proof): the range
+//                       is folded level by level between two scratch areas,
+//                       pairs across lanes; per level at most one left and one
+//                       right proof node join.  The proof's nodes are depth
+//                       first, so the first popcount(start) are the left
+//                       siblings top-down (taken in reverse), the rest the
+//                       right siblings bottom-up.
+//   3. vp_row_kernel    one lane per segment: sha256(0x00 || row root) against
+//                       the leaf hash, then the aunts bottom-up along the path
+//                       derived top-down from (index, total).
+//   4. vp_verdict_kernel one lane per proof: 1 if any row proof failed, else 2
+//                       if any NMT proof failed, else 0.
+// Every index a kernel uses was validated on the host (Engine::
+// share_proofs_verify); the counts that are verdicts (aunts, nodes) are
+// compared before anything is read through them.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/cda.h"
+#include "engine.h"
+#include "leaf_dev.h"
+#include "sha256_dev.h"
+
+namespace cda {
+
+namespace {
+
+struct VerifyBatch {
+    uint32_t n_proofs, n_segs, ns_len, share_len, node_len, stride;
+    const uint8_t* data_roots;   // NULL: no row half
+    const uint8_t* namespaces;
+    const uint32_t* seg_off;
+    const uint32_t* seg_proof;   // owning proof of every segment
+    const int32_t* nmt_start;
+    const int32_t* nmt_end;
+    const uint32_t* node_off;
+    const uint8_t* nodes;
+    const uint8_t* row_roots;
+    const int64_t* rfc_total;
+    const int64_t* rfc_index;
+    const uint8_t* rfc_leaf_hash;
+    const uint32_t* aunt_off;
+    const uint8_t* aunts;
+    const uint8_t* shares;       // NULL: no NMT half
+    const uint64_t* leaf_off;    // first share of every segment, n_segs + 1 entries
+    uint64_t n_shares;
+    uint8_t* buf_a;              // n_shares scratch nodes of `stride` bytes
+    uint8_t* buf_b;
+    uint8_t* node_slots;         // n_nodes slots: the proof nodes, aligned (29-byte namespaces)
+    uint8_t* nmt_ok;             // per segment
+    uint8_t* row_ok;
+    uint8_t* verdict;            // per proof
+};
+
+// SHA-256 of tag || a[0:na] || b[0:nb] (byte addressed, any lengths),
+// big-endian state words.
+__device__ void sha_cat(uint32_t tag, const uint8_t* a, uint32_t na, const uint8_t* b, uint32_t nb,
+                        uint32_t (&out)[8]) {
+    ShaState st;
+    sha_init(st);
+    const uint32_t total = 1 + na + nb;
+    const uint32_t n_blocks = (total + 9 + 63) / 64;
+    auto byte_at = [&](uint32_t i) -> uint32_t {
+        if (i == 0) return tag;
+        if (i <= na) return a[i - 1];
+        if (i < total) return b[i - 1 - na];
+        if (i == total) return 0x80u;
+        return 0;
+    };
+#pragma unroll 1
+    for (uint32_t blk = 0; blk < n_blocks; blk++) {
+        uint32_t w[16];
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const uint32_t p = blk * 64 + 4 * j;
+            w[j] = (byte_at(p) << 24) | (byte_at(p + 1) << 16) | (byte_at(p + 2) << 8) | byte_at(p + 3);
+        }
+        if (blk == n_blocks - 1) {
+            w[14] = 0;
+            w[15] = total * 8;
+        }
+        sha_compress(st, w);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) out[j] = st.h[j];
+}
+
+__device__ __forceinline__ void store_digest_bytes(uint8_t* o, const uint32_t (&d)[8]) {
+    for (int j = 0; j < 8; j++) {
+        o[4 * j + 0] = (uint8_t)(d[j] >> 24);
+        o[4 * j + 1] = (uint8_t)(d[j] >> 16);
+        o[4 * j + 2] = (uint8_t)(d[j] >> 8);
+        o[4 * j + 3] = (uint8_t)d[j];
+    }
+}
+
+// Big-endian words of 32 bytes at a 4-byte aligned address.
+__device__ __forceinline__ void load_digest_be(const uint8_t* p, uint32_t (&d)[8]) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+    for (int j = 0; j < 8; j++) d[j] = bswap32(q[j]);
+}
+
+// Big-endian slot words of a packed 90-B node at any byte address.
+__device__ __forceinline__ void load_packed_be(const uint8_t* p, uint32_t (&w)[kSlotWords]) {
+#pragma unroll
+    for (int t = 0; t < 22; t++)
+        w[t] = ((uint32_t)p[4 * t] << 24) | ((uint32_t)p[4 * t + 1] << 16) | ((uint32_t)p[4 * t + 2] << 8) | p[4 * t + 3];
+    w[22] = ((uint32_t)p[88] << 24) | ((uint32_t)p[89] << 16);
+    w[23] = 0;
+}
+
+// The 29-byte, 512-byte leaf digest sha256(0x00 || ns || share): leaf_dev.h's
+// streaming of the share (64-B chunks of raw words, one v_perm per message
+// word) with the namespace given by the proof instead of read from the share.
+// nsw: big-endian namespace words (byte 28 in the top byte of nsw[7]).
+__device__ __forceinline__ void leaf29_digest(const uint8_t* __restrict__ share, const uint32_t (&nsw)[8],
+                                              uint32_t (&d)[8]) {
+    const uint4* src = reinterpret_cast<const uint4*>(share);
+    ShaState st;
+    sha_init(st);
+    uint32_t cur[16], nxt[16], tail[8], w[16];
+    load_raw16(src, cur);
+    load_raw16(src + 4, nxt);
+    // block 0: 0x00 || ns(29) || share[0:34]
+    w[0] = nsw[0] >> 8;
+#pragma unroll
+    for (int i = 1; i < 7; i++) w[i] = funnel8(nsw[i - 1], nsw[i], 1);
+    w[7] = (nsw[6] << 24) | ((nsw[7] >> 24) << 16) | __builtin_amdgcn_perm(cur[0], cur[0], 0x0C0C0001u);
+#pragma unroll
+    for (int i = 8; i < 16; i++) w[i] = body_word(cur[i - 8], cur[i - 7]);
+    sha_compress(st, w);
+#pragma unroll
+    for (int i = 0; i < 8; i++) tail[i] = cur[8 + i];
+#pragma unroll 1
+    for (int b = 1; b < 8; b++) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) cur[i] = nxt[i];
+        if (b < 7) load_raw16(src + 4 * (b + 1), nxt);
+#pragma unroll
+        for (int t = 0; t < 7; t++) w[t] = body_word(tail[t], tail[t + 1]);
+        w[7] = body_word(tail[7], cur[0]);
+#pragma unroll
+        for (int t = 8; t < 16; t++) w[t] = body_word(cur[t - 8], cur[t - 7]);
+#pragma unroll
+        for (int i = 0; i < 8; i++) tail[i] = cur[8 + i];
+        sha_compress(st, w);
+    }
+    // block 8: share words 120..127 then padding (542-B message)
+#pragma unroll
+    for (int t = 0; t < 7; t++) w[t] = body_word(tail[t], tail[t + 1]);
+    w[7] = __builtin_amdgcn_perm(tail[7], tail[7], 0x02030C0Cu) | 0x8000u;
+#pragma unroll
+    for (int t = 8; t < 15; t++) w[t] = 0;
+    w[15] = kLeafMsgBits;
+    sha_compress(st, w);
+#pragma unroll
+    for (int j = 0; j < 8; j++) d[j] = st.h[j];
+}
+
+// Leaf nodes of every share of the batch.  FAST: ns_len 29, share_len 512,
+// 96-B slots; otherwise byte nodes of node_len bytes at `stride`.
+template <bool FAST>
+__global__ __launch_bounds__(256) void vp_leaf_kernel(const VerifyBatch b) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= b.n_shares) return;
+    // the segment that owns share i: leaf_off[s] <= i < leaf_off[s + 1]
+    uint32_t lo = 0, hi = b.n_segs;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (b.leaf_off[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    const uint8_t* nid = b.namespaces + (size_t)b.seg_proof[lo] * b.ns_len;
+    const uint8_t* share = b.shares + i * b.share_len;
+    uint8_t* out = b.buf_a + i * b.stride;
+    uint32_t d[8];
+    if constexpr (FAST) {
+        uint32_t nsw[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int q = 0; q < 4; q++)
+                if (4 * j + q < kNs) v |= (uint32_t)nid[4 * j + q] << (24 - 8 * q);
+            nsw[j] = v;
+        }
+        leaf29_digest(share, nsw, d);
+        uint32_t o[kSlotWords];
+        leaf_node_words(nsw, d, o);
+        store_slot(out, o);
+    } else {
+        sha_cat(0x00, nid, b.ns_len, share, b.share_len, d);
+        for (uint32_t j = 0; j < b.ns_len; j++) out[j] = out[b.ns_len + j] = nid[j];
+        store_digest_bytes(out + 2 * b.ns_len, d);
+    }
+}
+
+// nmt HashNode with IgnoreMaxNamespace(true): min of the left, max of the
+// right unless the right's min is all 0xFF (then max of the left), the digest
+// of 0x01 || left || right.  FAST: l / r / out are 96-B slots (the proof's
+// nodes were copied into slots first); otherwise nodes of node_len bytes at
+// any address.
+template <bool FAST>
+__device__ __forceinline__ void vp_hash_node(uint32_t ns, const uint8_t* l, const uint8_t* r, uint8_t* out) {
+    if constexpr (FAST) {
+        uint32_t L[kSlotWords], R[kSlotWords], o[kSlotWords];
+        load_slot_be(l, L);
+        load_slot_be(r, R);
+        hash_node_u<false>(L, R, o, false);
+        store_slot(out, o);
+    } else {
+        const uint32_t N = 2 * ns + 32;
+        bool ign = true;
+        for (uint32_t j = 0; j < ns; j++) ign = ign && r[j] == 0xFFu;
+        const uint8_t* mx = ign ? l + ns : r + ns;
+        for (uint32_t j = 0; j < ns; j++) {
+            out[j] = l[j];
+            out[ns + j] = mx[j];
+        }
+        uint32_t d[8];
+        sha_cat(0x01, l, N, r, N, d);
+        store_digest_bytes(out + 2 * ns, d);
+    }
+}
+
+// One segment per workgroup of one wave.
+template <bool FAST>
+__global__ __launch_bounds__(64) void vp_fold_kernel(const VerifyBatch b) {
+    const uint32_t s = blockIdx.x, tid = threadIdx.x;
+    if (s >= b.n_segs) return;
+    const uint32_t start = (uint32_t)b.nmt_start[s], end = (uint32_t)b.nmt_end[s];   // 0 <= start < end <= 2048
+    const uint32_t n0 = b.node_off[s], m = b.node_off[s + 1] - n0;
+    const uint32_t N = b.node_len, stride = b.stride;
+    const uint32_t n_left = (uint32_t)__popc(start);
+    uint32_t levels = 0;
+    while ((1u << levels) < end) levels++;   // the subtree of pow2ceil(end) leaves
+    // Too few nodes for the range, or more than any tree has: at most one
+    // right sibling per level of the subtree and 63 beyond it (the leaf count
+    // of an nmt is a Go int).  Uniform over the workgroup.
+    if (m < n_left || m - n_left > levels + 63) {
+        if (tid == 0) b.nmt_ok[s] = 0;
+        return;
+    }
+    // the segment's proof nodes: read where they lie, or (FAST) copied into
+    // 16-byte aligned slots so that every node load is a slot load
+    const uint8_t* nodes = b.nodes + (size_t)n0 * N;
+    uint32_t nstride = N;
+    if constexpr (FAST) {
+        uint8_t* slots = b.node_slots + (size_t)n0 * kSlot;
+        for (uint32_t q = tid; q < m * (uint32_t)kSlot; q += 64) {
+            const uint32_t node = q / kSlot, o = q % kSlot;
+            slots[q] = o < (uint32_t)kNode ? nodes[(size_t)node * kNode + o] : (uint8_t)0;
+        }
+        nodes = slots;
+        nstride = kSlot;
+        __syncthreads();
+    }
+    uint32_t li = n_left;   // left siblings still to take: node li - 1 is next
+    uint32_t ri = n_left;   // next right sibling, while ri < m
+    const uint64_t base = b.leaf_off[s] * stride;
+    uint8_t* src = b.buf_a + base;
+    uint8_t* dst = b.buf_b + base;
+    uint32_t lo = start, hi = end;
+    // the levels of the subtree; after them [lo, hi) = [0, 1) and the same
+    // step takes the nodes that remain, which lie to the right of the subtree
+    for (uint32_t lvl = 0; lvl < levels || ri < m; lvl++) {
+        const bool need_l = lo & 1, need_r = hi & 1;
+        const bool has_r = need_r && ri < m;
+        const uint32_t nlo = lo >> 1, nhi = (hi + 1) >> 1, cnt = nhi - nlo;
+        for (uint32_t j = tid; j < cnt; j += 64) {
+            const uint32_t p0 = 2 * (nlo + j), p1 = p0 + 1;
+            const bool l_proof = p0 < lo;     // p0 == lo - 1: the left sibling of the range
+            const bool r_out = p1 >= hi;      // p1 == hi: right of the range
+            const uint8_t* l = l_proof ? nodes + (size_t)(li - 1) * nstride : src + (size_t)(p0 - lo) * stride;
+            uint8_t* o = dst + (size_t)j * stride;
+            if (r_out && !has_r) {
+                // no node on the right: the unpaired node goes up unchanged
+                // (p0 is inside the range here: lo <= hi - 1 = p0)
+                for (uint32_t q = 0; q < stride; q += 4)
+                    *reinterpret_cast<uint32_t*>(o + q) = *reinterpret_cast<const uint32_t*>(l + q);
+            } else {
+                const uint8_t* r = r_out ? nodes + (size_t)ri * nstride : src + (size_t)(p1 - lo) * stride;
+                vp_hash_node<FAST>(b.ns_len, l, r, o);
+            }
+        }
+        if (need_l) li--;
+        if (has_r) ri++;
+        lo = nlo;
+        hi = nhi;
+        uint8_t* t = src;
+        src = dst;
+        dst = t;
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    const uint8_t* root = b.row_roots + (size_t)s * N;
+    bool ok = true;
+    for (uint32_t j = 0; j < N; j++) ok = ok && src[j] == root[j];
+    b.nmt_ok[s] = ok ? 1 : 0;
+}
+
+// merkle Proof.Verify of one row root per lane.
+__global__ __launch_bounds__(256) void vp_row_kernel(const VerifyBatch b) {
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= b.n_segs) return;
+    const int64_t total = b.rfc_total[s], index = b.rfc_index[s];
+    const uint32_t a0 = b.aunt_off[s], na = b.aunt_off[s + 1] - a0;
+    bool ok = total > 0 && index >= 0 && index < total;
+    uint64_t right = 0;   // bit d: at depth d (0 = below the root) the path goes right
+    if (ok) {
+        uint64_t t = (uint64_t)total, i = (uint64_t)index;
+        uint32_t depth = 0;
+        while (t > 1) {   // at most 63 levels
+            const uint64_t k = 1ull << (63 - __clzll((long long)(t - 1)));   // largest power of two below t
+            if (i < k) {
+                t = k;
+            } else {
+                right |= 1ull << depth;
+                i -= k;
+                t -= k;
+            }
+            depth++;
+        }
+        ok = depth == na;
+    }
+    uint32_t h[8];
+    if (ok) {
+        const uint8_t* row_root = b.row_roots + (size_t)s * b.node_len;
+        uint32_t d[8];
+        if (b.node_len == (uint32_t)kNode) {
+            uint32_t I[kSlotWords];
+            load_packed_be(row_root, I);
+            rfc_leaf_u<false>(I, d, false);
+        } else {
+            sha_cat(0x00, row_root, b.node_len, row_root, 0, d);
+        }
+        load_digest_be(b.rfc_leaf_hash + (size_t)s * 32, h);
+#pragma unroll
+        for (int j = 0; j < 8; j++) ok = ok && d[j] == h[j];
+    }
+    if (ok) {
+#pragma unroll 1
+        for (uint32_t i = 0; i < na; i++) {
+            uint32_t a[8], o[8];
+            load_digest_be(b.aunts + (size_t)(a0 + i) * 32, a);
+            if ((right >> (na - 1 - i)) & 1) rfc_inner_u<false>(a, h, o, false);
+            else rfc_inner_u<false>(h, a, o, false);
+#pragma unroll
+            for (int j = 0; j < 8; j++) h[j] = o[j];
+        }
+        uint32_t want[8];
+        load_digest_be(b.data_roots + (size_t)b.seg_proof[s] * 32, want);
+#pragma unroll
+        for (int j = 0; j < 8; j++) ok = ok && h[j] == want[j];
+    }
+    b.row_ok[s] = ok ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void vp_verdict_kernel(const VerifyBatch b) {
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= b.n_proofs) return;
+    uint32_t v = 0;
+    for (uint32_t s = b.seg_off[p]; s < b.seg_off[p + 1]; s++) {
+        if (b.data_roots && !b.row_ok[s]) v = 1;
+        else if (b.shares && !b.nmt_ok[s] && v == 0) v = 2;
+    }
+    b.verdict[p] = (uint8_t)v;
+}
+
+std::string at(uint32_t proof, const char* what) { return "proof " + std::to_string(proof) + ": " + what; }
+
+}  // namespace
+
+int Engine::share_proofs_verify(const cda_share_proof_batch* b, uint8_t* verdict) {
+    if (!b) return fail(CDA_ERR_INVALID, "null batch");
+    const uint32_t P = b->n_proofs;
+    if (P == 0) return CDA_OK;
+    if (!verdict) return fail(CDA_ERR_INVALID, "null verdict buffer");
+    if (b->ns_len < 1 || b->ns_len > CDA_VERIFY_MAX_NS)
+        return fail(CDA_ERR_INVALID, "ns_len " + std::to_string(b->ns_len) + " out of range [1, " +
+                                         std::to_string(CDA_VERIFY_MAX_NS) + "]");
+    if (!b->namespaces || !b->seg_off) return fail(CDA_ERR_INVALID, "null namespaces / seg_off");
+    const bool rows = b->data_roots != nullptr, nmt = b->shares != nullptr;
+    if (b->seg_off[0] != 0) return fail(CDA_ERR_INVALID, at(0, "seg_off must start at 0"));
+    for (uint32_t p = 0; p < P; p++)
+        if (b->seg_off[p + 1] < b->seg_off[p]) return fail(CDA_ERR_INVALID, at(p, "seg_off decreases"));
+    const uint32_t S = b->seg_off[P];
+    if (S && !b->row_roots) return fail(CDA_ERR_INVALID, "null row_roots");
+    if (S && rows && (!b->rfc_total || !b->rfc_index || !b->rfc_leaf_hash || !b->aunt_off || (b->n_aunts && !b->aunts)))
+        return fail(CDA_ERR_INVALID, "null row proof field (rfc_total / rfc_index / rfc_leaf_hash / aunt_off / aunts)");
+    if (S && nmt && (!b->nmt_start || !b->nmt_end || !b->node_off || (b->n_nodes && !b->nodes)))
+        return fail(CDA_ERR_INVALID, "null NMT proof field (nmt_start / nmt_end / node_off / nodes)");
+    std::vector<uint32_t> seg_proof(S);
+    for (uint32_t p = 0; p < P; p++)
+        for (uint32_t s = b->seg_off[p]; s < b->seg_off[p + 1]; s++) seg_proof[s] = p;
+    std::vector<uint64_t> leaf_off(S + 1, 0);
+    if (nmt && S) {
+        if (b->node_off[0] != 0) return fail(CDA_ERR_INVALID, at(0, "node_off must start at 0"));
+        for (uint32_t s = 0; s < S; s++) {
+            const int32_t st = b->nmt_start[s], en = b->nmt_end[s];
+            const std::string seg = "segment " + std::to_string(s) + ": ";
+            if (st < 0) return fail(CDA_ERR_INVALID, at(seg_proof[s], (seg + "nmt_start " + std::to_string(st) + " is negative").c_str()));
+            if (en <= st)
+                return fail(CDA_ERR_INVALID, at(seg_proof[s], (seg + "nmt_end " + std::to_string(en) +
+                                                               " is not above nmt_start " + std::to_string(st)).c_str()));
+            if (en > CDA_VERIFY_MAX_LEAVES)
+                return fail(CDA_ERR_INVALID, at(seg_proof[s], (seg + "nmt_end " + std::to_string(en) + " exceeds " +
+                                                               std::to_string(CDA_VERIFY_MAX_LEAVES)).c_str()));
+            if (b->node_off[s + 1] < b->node_off[s])
+                return fail(CDA_ERR_INVALID, at(seg_proof[s], (seg + "node_off decreases").c_str()));
+            leaf_off[s + 1] = leaf_off[s] + (uint64_t)(en - st);
+        }
+        if (b->node_off[S] != b->n_nodes)
+            return fail(CDA_ERR_INVALID, "node_off ends at " + std::to_string(b->node_off[S]) + ", n_nodes is " +
+                                             std::to_string(b->n_nodes));
+        if (leaf_off[S] != b->n_shares)
+            return fail(CDA_ERR_INVALID, "n_shares is " + std::to_string(b->n_shares) +
+                                             ", the segments' nmt_end - nmt_start sum to " + std::to_string(leaf_off[S]));
+    }
+    if (rows && S) {
+        if (b->aunt_off[0] != 0) return fail(CDA_ERR_INVALID, at(0, "aunt_off must start at 0"));
+        for (uint32_t s = 0; s < S; s++)
+            if (b->aunt_off[s + 1] < b->aunt_off[s])
+                return fail(CDA_ERR_INVALID,
+                            at(seg_proof[s], ("segment " + std::to_string(s) + ": aunt_off decreases").c_str()));
+        if (b->aunt_off[S] != b->n_aunts)
+            return fail(CDA_ERR_INVALID, "aunt_off ends at " + std::to_string(b->aunt_off[S]) + ", n_aunts is " +
+                                             std::to_string(b->n_aunts));
+    }
+
+    hipStream_t s = stream_;
+    const uint32_t N = 2 * b->ns_len + 32;
+    const bool fast = b->ns_len == (uint32_t)kNs && b->share_len == (uint32_t)kShare;
+    const uint32_t stride = fast ? (uint32_t)kSlot : (N + 3u) & ~3u;
+    const uint64_t n_shares = nmt ? leaf_off[S] : 0;
+
+    // one input buffer, every array at a 16-byte boundary
+    struct Piece {
+        const void* host;
+        size_t bytes, off;
+    };
+    size_t total = 0;
+    auto piece = [&](const void* host, size_t bytes) {
+        Piece pc{host, host ? bytes : 0, total};
+        total += (pc.bytes + 15) & ~(size_t)15;
+        return pc;
+    };
+    const Piece p_roots = piece(b->data_roots, (size_t)P * 32), p_ns = piece(b->namespaces, (size_t)P * b->ns_len),
+                p_seg = piece(b->seg_off, (size_t)(P + 1) * 4), p_sp = piece(seg_proof.data(), (size_t)S * 4),
+                p_st = piece(nmt ? b->nmt_start : nullptr, (size_t)S * 4),
+                p_en = piece(nmt ? b->nmt_end : nullptr, (size_t)S * 4),
+                p_no = piece(nmt ? b->node_off : nullptr, (size_t)(S + 1) * 4),
+                p_nodes = piece(nmt ? b->nodes : nullptr, (size_t)b->n_nodes * N),
+                p_rr = piece(b->row_roots, (size_t)S * N), p_tot = piece(rows ? b->rfc_total : nullptr, (size_t)S * 8),
+                p_idx = piece(rows ? b->rfc_index : nullptr, (size_t)S * 8),
+                p_lh = piece(rows ? b->rfc_leaf_hash : nullptr, (size_t)S * 32),
+                p_ao = piece(rows ? b->aunt_off : nullptr, (size_t)(S + 1) * 4),
+                p_aunts = piece(rows ? b->aunts : nullptr, (size_t)b->n_aunts * 32),
+                p_lo = piece(leaf_off.data(), (size_t)(S + 1) * 8),
+                p_sh = piece(nmt ? b->shares : nullptr, (size_t)n_shares * b->share_len);
+    int rc;
+    if ((rc = check(vp_in_.ensure(total + 16), "hipMalloc proof batch"))) return rc;
+    const size_t scr_nodes = ((size_t)n_shares * stride + 15) & ~(size_t)15;
+    const size_t flags = ((size_t)S + 15) & ~(size_t)15;
+    const size_t node_slots = fast && nmt ? (size_t)b->n_nodes * kSlot : 0;
+    if ((rc = check(vp_scratch_.ensure(2 * scr_nodes + node_slots + 2 * flags + P + 16), "hipMalloc proof scratch")))
+        return rc;
+    uint8_t* in = vp_in_.as<uint8_t>();
+    for (const Piece* pc : {&p_roots, &p_ns, &p_seg, &p_sp, &p_st, &p_en, &p_no, &p_nodes, &p_rr, &p_tot, &p_idx, &p_lh,
+                            &p_ao, &p_aunts, &p_lo, &p_sh})
+        if (pc->bytes &&
+            (rc = check(hipMemcpyAsync(in + pc->off, pc->host, pc->bytes, hipMemcpyHostToDevice, s), "H2D proof batch")))
+            return rc;
+    auto dev = [&](const Piece& pc) -> const uint8_t* { return pc.host ? in + pc.off : nullptr; };
+    uint8_t* scr = vp_scratch_.as<uint8_t>();
+    VerifyBatch v{};
+    v.n_proofs = P;
+    v.n_segs = S;
+    v.ns_len = b->ns_len;
+    v.share_len = b->share_len;
+    v.node_len = N;
+    v.stride = stride;
+    v.data_roots = dev(p_roots);
+    v.namespaces = dev(p_ns);
+    v.seg_off = reinterpret_cast<const uint32_t*>(dev(p_seg));
+    v.seg_proof = reinterpret_cast<const uint32_t*>(in + p_sp.off);
+    v.nmt_start = reinterpret_cast<const int32_t*>(dev(p_st));
+    v.nmt_end = reinterpret_cast<const int32_t*>(dev(p_en));
+    v.node_off = reinterpret_cast<const uint32_t*>(dev(p_no));
+    v.nodes = in + p_nodes.off;
+    v.row_roots = in + p_rr.off;
+    v.rfc_total = reinterpret_cast<const int64_t*>(dev(p_tot));
+    v.rfc_index = reinterpret_cast<const int64_t*>(dev(p_idx));
+    v.rfc_leaf_hash = dev(p_lh);
+    v.aunt_off = reinterpret_cast<const uint32_t*>(dev(p_ao));
+    v.aunts = in + p_aunts.off;
+    v.shares = nmt ? in + p_sh.off : nullptr;
+    v.leaf_off = reinterpret_cast<const uint64_t*>(in + p_lo.off);
+    v.n_shares = n_shares;
+    v.buf_a = scr;
+    v.buf_b = scr + scr_nodes;
+    v.node_slots = scr + 2 * scr_nodes;
+    v.nmt_ok = v.node_slots + node_slots;
+    v.row_ok = v.nmt_ok + flags;
+    v.verdict = v.row_ok + flags;
+    if (nmt && S) {
+        const dim3 grid((uint32_t)((n_shares + 255) / 256));
+        if (fast) hipLaunchKernelGGL(vp_leaf_kernel<true>, grid, dim3(256), 0, s, v);
+        else hipLaunchKernelGGL(vp_leaf_kernel<false>, grid, dim3(256), 0, s, v);
+        if ((rc = check(hipGetLastError(), "proof leaves"))) return rc;
+        if (fast) hipLaunchKernelGGL(vp_fold_kernel<true>, dim3(S), dim3(64), 0, s, v);
+        else hipLaunchKernelGGL(vp_fold_kernel<false>, dim3(S), dim3(64), 0, s, v);
+        if ((rc = check(hipGetLastError(), "proof range fold"))) return rc;
+    }
+    if (rows && S) {
+        hipLaunchKernelGGL(vp_row_kernel, dim3((S + 255) / 256), dim3(256), 0, s, v);
+        if ((rc = check(hipGetLastError(), "row proofs"))) return rc;
+    }
+    hipLaunchKernelGGL(vp_verdict_kernel, dim3((P + 255) / 256), dim3(256), 0, s, v);
+    if ((rc = check(hipGetLastError(), "proof verdicts"))) return rc;
+    std::vector<uint8_t> out(P);
+    if ((rc = check(hipMemcpyAsync(out.data(), v.verdict, P, hipMemcpyDeviceToHost, s), "D2H verdicts"))) return rc;
+    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
+    memcpy(verdict, out.data(), P);
+    return CDA_OK;
+}
+
+}  // namespace cda

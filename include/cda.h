@@ -41,6 +41,10 @@
  *                          Root / ProveRange (pkg/wrapper/nmt_wrapper.go:55-129)
  *   cda_merkle_root        go-square/merkle HashFromByteSlices (DAH.Hash for
  *                          any root count, data_availability_header.go:92-108)
+ *   cda_share_proofs_verify
+ *                          ShareProof.Validate / VerifyProof and RowProof.Validate
+ *                          (pkg/proof/share_proof.go:16-82, row_proof.go:13-51),
+ *                          batched
  *   cda_comm_* / cda_extend_dah_split / cda_extend_dah_multi
  *                          multi-GPU configs 4 and 5 (app/process_proposal.go:138-152
  *                          block replay; one square over G GPUs)
@@ -490,6 +494,57 @@ int cda_nmt_prove_range(cda_ctx *ctx, const uint8_t *cells, uint32_t cell_len, u
  * .Hash for any root count and size (data_availability_header.go:92-108).
  * n == 0 gives sha256(""). */
 int cda_merkle_root(cda_ctx *ctx, const uint8_t *items, const uint64_t *off, uint32_t n, uint8_t out[32]);
+
+/* ---- Proof verification (the verifying side) ----------
+ * The hashed halves of ShareProof.Validate / VerifyProof
+ * (pkg/proof/share_proof.go:16-82) and RowProof.Validate
+ * (pkg/proof/row_proof.go:13-51) for a batch of independent proofs in one
+ * submission: per row of a proof (a "segment") nmt Proof.VerifyInclusion of the
+ * row's shares against the row root (EXT nmt v0.22.0, IgnoreMaxNamespace) and
+ * go-square/merkle Proof.Verify of the row root against the data root (EXT
+ * v1.1.0; any Total, RFC-6962 split).  The structural checks of Validate
+ * (counts, negative start, ...) are the caller's (celestia_da.proof).
+ * The batch is flat (CSR offsets), so one call takes any mix of proofs; the
+ * namespace size is the batch's (the reference's own vector uses 33 bytes):
+ * ns_len = 29 with 512-byte shares runs the square's leaf hashing, any other
+ * size byte-addressed kernels.
+ * Checked on the host before anything is enqueued, CDA_ERR_INVALID with a
+ * message naming the proof and the field (verdict is then left untouched):
+ * offsets start at 0, never decrease and end at n_nodes / n_aunts; the sum of
+ * nmt_end - nmt_start equals n_shares; 1 <= ns_len <= CDA_VERIFY_MAX_NS;
+ * 0 <= nmt_start < nmt_end <= CDA_VERIFY_MAX_LEAVES.
+ * Verdicts, not errors: rfc_total <= 0, rfc_index outside [0, total) or an
+ * aunt count that is not the path's depth (1); too few or too many NMT nodes
+ * for the range (2).  n_proofs == 0 returns CDA_OK. */
+#define CDA_VERIFY_MAX_NS 64        /* bytes of version||id */
+#define CDA_VERIFY_MAX_LEAVES 2048  /* NMTProof.End bound: the widest row the library builds (k = 1024) */
+typedef struct cda_share_proof_batch {
+    uint32_t n_proofs;
+    uint32_t ns_len;               /* 1 + len(NamespaceId); 29 on Celestia; node size N = 2*ns_len + 32 */
+    uint32_t share_len;            /* bytes per ShareProof.Data item (512) */
+    const uint8_t *data_roots;     /* n_proofs*32; NULL = skip the RowProof half */
+    const uint8_t *namespaces;     /* n_proofs*ns_len: version || id */
+    const uint32_t *seg_off;       /* n_proofs+1; proof p owns segments (rows) [seg_off[p], seg_off[p+1]); S = last */
+    const int32_t *nmt_start;      /* S: NMTProof.Start */
+    const int32_t *nmt_end;        /* S: NMTProof.End */
+    const uint32_t *node_off;      /* S+1 offsets into nodes, in nodes of N bytes */
+    const uint8_t *nodes;          /* n_nodes*N: NMTProof.Nodes */
+    uint32_t n_nodes;
+    const uint8_t *row_roots;      /* S*N: RowProof.RowRoots */
+    const int64_t *rfc_total;      /* S: Proof.Total */
+    const int64_t *rfc_index;      /* S: Proof.Index */
+    const uint8_t *rfc_leaf_hash;  /* S*32: Proof.LeafHash */
+    const uint32_t *aunt_off;      /* S+1 offsets into aunts, in aunts of 32 bytes */
+    const uint8_t *aunts;          /* n_aunts*32: Proof.Aunts, bottom-up */
+    uint32_t n_aunts;
+    const uint8_t *shares;         /* n_shares*share_len: ShareProof.Data, concatenated in proof then segment
+                                      order; NULL = skip the NMT half (nmt_*, node*, n_shares are then unused) */
+    uint64_t n_shares;
+} cda_share_proof_batch;
+/* verdict[p] (n_proofs bytes): 0 valid, 1 "row proof failed to verify", 2
+ * "share proof failed to verify" (1 wins, as Validate runs the row proof
+ * first).  Host buffers; complete when the call returns. */
+int cda_share_proofs_verify(cda_ctx *ctx, const cda_share_proof_batch *b, uint8_t *verdict);
 
 /* Stage timing (HIP events on the launch stream).  When enabled, every
  * enqueued stage is bracketed by events; cda_stage_times synchronises them and
