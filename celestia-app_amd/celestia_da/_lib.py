@@ -68,8 +68,11 @@ EXPORTED = (
     "cda_nmt_axis_roots", "cda_nmt_axis_root", "cda_nmt_prove_range", "cda_merkle_root",
     "cda_comm_unique_id", "cda_comm_init", "cda_comm_destroy", "cda_comm_size", "cda_comm_abort", "cda_extend_dah_split", "cda_split_rows_send",
     "cda_extend_dah_multi", "cda_split_layout", "cda_split_offsets", "cda_extend_dah_batch_ex",
-    "cda_share_proofs_verify",
+    "cda_share_proofs_verify", "cda_square_sample_proofs", "cda_sample_proofs_verify",
 )
+# cda_square_sample_proofs axes (include/cda.h)
+CDA_AXIS_ROW = 0
+CDA_AXIS_COL = 1
 STAGES = ("rs_q0", "rs_q3", "order_check", "nmt_leaves", "nmt_levels", "data_root")
 
 
@@ -207,6 +210,9 @@ def load(path: str | None = None):
                                           C.c_uint32, u8p, u32p, u8p]
         L.cda_merkle_root.argtypes = [ctxp, u8p, u64p, C.c_uint32, u8p]
         L.cda_share_proofs_verify.argtypes = [ctxp, C.POINTER(ShareProofBatch), u8p]
+        L.cda_square_sample_proofs.argtypes = [vp, u32p, u32p, u8p, C.c_uint32, u8p, u8p, u8p, u8p, u8p, u8p]
+        L.cda_sample_proofs_verify.argtypes = [ctxp, C.c_uint32, C.c_uint32, u8p, u32p, u32p, u8p, u8p, u8p, u8p,
+                                               u8p, u8p, u8p]
         L.cda_comm_unique_id.argtypes = [u8p]
         L.cda_comm_init.argtypes = [ctxp, C.c_int, C.c_int, u8p]
         L.cda_comm_destroy.argtypes = [ctxp]

@@ -210,6 +210,15 @@ class ResidentSquare:
                           row_proof=RowProof([rb[90 * i:90 * (i + 1)] for i in range(R)], proofs, r0.value, r1.value),
                           namespace_version=namespace[0])
 
+    def sample_proofs(self, coords, out=None):
+        """Data-availability samples of the EDS (cda_square_sample_proofs):
+        coords is an (n, 3) integer array of (row, col, axis), 0 <= row, col <
+        2k, axis 0 = against the row root, 1 = against the column root (an
+        (n, 2) array: all on the row axis).  One launch for the whole batch;
+        returns a sampling.SampleBatch."""
+        from . import sampling
+        return sampling.sample_proofs(self, coords, out)
+
     def blob_commitments(self, starts, share_lens, subtree_root_threshold: int = 64):
         """inclusion.GetCommitment for each (start, share_len)."""
         n = len(starts)

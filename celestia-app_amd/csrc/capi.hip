@@ -587,6 +587,26 @@ int cda_square_subtree_root(cda_square* sq, uint32_t row, const uint8_t* walk, u
     });
 }
 
+int cda_square_sample_proofs(cda_square* sq, const uint32_t* rows, const uint32_t* cols, const uint8_t* axes,
+                             uint32_t n, uint8_t* shares, uint8_t* namespaces, uint8_t* nmt_nodes,
+                             uint8_t* axis_roots, uint8_t* leaf_hash, uint8_t* aunts) {
+    if (!sq) return CDA_ERR_INVALID;
+    return guarded(sq->ctx, [&](cda::Engine& e) -> int {
+        const cda::Engine::SampleOut o{shares, namespaces, nmt_nodes, axis_roots, leaf_hash, aunts};
+        return e.square_sample_proofs(&sq->sq, rows, cols, axes, n, o);
+    });
+}
+
+int cda_sample_proofs_verify(cda_ctx* ctx, uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
+                             const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,
+                             const uint8_t* nmt_nodes, const uint8_t* axis_roots, const uint8_t* leaf_hash,
+                             const uint8_t* aunts, uint8_t* verdict) {
+    return guarded(ctx, [&](cda::Engine& e) -> int {
+        return e.sample_proofs_verify(k, n, data_roots, rows, cols, axes, shares, nmt_nodes, axis_roots, leaf_hash,
+                                      aunts, verdict);
+    });
+}
+
 int cda_repair(cda_ctx* ctx, uint8_t* eds, const uint8_t* present, uint32_t w, const uint8_t* row_roots,
                const uint8_t* col_roots, int32_t* byz_axis, uint32_t* byz_index) {
     return guarded(ctx, [&](cda::Engine& e) -> int {

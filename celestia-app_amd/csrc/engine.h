@@ -90,12 +90,15 @@ hipError_t launch_slot_merkle_roots(const uint8_t* slots, const uint32_t* bt, ui
 
 // A square kept in HBM after extension (proof.hip): the EDS, every level of
 // every row tree (level 0 = the W x W leaf slots, level L = [W][W >> L] 96-B
-// slots), the roots and all RFC-6962 levels of the data-root tree.
+// slots), levels 1.. of every column tree (level L = [W columns][W >> L];
+// level 0 of a column is the leaf level read with stride W), the roots and
+// all RFC-6962 levels of the data-root tree.
 struct ResidentSquare {
     enum Part { kRowRoots, kColRoots, kDataRoot, kEds };
     uint32_t k = 0, log_w = 0, push_err = 0xFFFFFFFFu;
-    DevBuf eds, levels, col_a, col_b, roots_slots, rfc, rows, cols, root, err, scratch, pieces;
-    uint64_t level_offset(uint32_t L) const;
+    DevBuf eds, levels, col_levels, roots_slots, rfc, rows, cols, root, err, scratch, pieces;
+    uint64_t level_offset(uint32_t L) const;       // bytes into `levels`, L >= 0
+    uint64_t col_level_offset(uint32_t L) const;   // bytes into `col_levels`, L >= 1
     ~ResidentSquare();
 };
 // One copy out of a resident square (byte offsets into the named buffer).
@@ -266,6 +269,23 @@ class Engine {
     int square_subtree_root(ResidentSquare* sq, uint32_t row, const uint8_t* walk, uint32_t walk_len, uint8_t* out);
     int square_blob_commitments(ResidentSquare* sq, const uint32_t* starts, const uint32_t* lens, uint32_t n,
                                 uint32_t threshold, uint8_t* out);
+    // Data-availability samples (sample.hip): n cells of the EDS with their
+    // proofs in one launch; any output may be NULL (strides in include/cda.h).
+    struct SampleOut {
+        uint8_t* shares;       // [n][512]
+        uint8_t* namespaces;   // [n][29]
+        uint8_t* nmt_nodes;    // [n][log2(2k)][90]
+        uint8_t* axis_roots;   // [n][90]
+        uint8_t* leaf_hash;    // [n][32]
+        uint8_t* aunts;        // [n][log2(4k)][32]
+    };
+    int square_sample_proofs(ResidentSquare* sq, const uint32_t* rows, const uint32_t* cols, const uint8_t* axes,
+                             uint32_t n, const SampleOut& out);
+    // The verifying side: the batch of share_proofs_verify built from the coordinates.
+    int sample_proofs_verify(uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
+                             const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,
+                             const uint8_t* nmt_nodes, const uint8_t* axis_roots, const uint8_t* leaf_hash,
+                             const uint8_t* aunts, uint8_t* verdict);
 
     // Repair (repair.hip): rsmt2d ExtendedDataSquare.Repair and Codec.Decode.
     int host_repair(uint8_t* eds, const uint8_t* present, uint32_t w, const uint8_t* row_roots,

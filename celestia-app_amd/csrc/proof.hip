@@ -11,6 +11,7 @@
 // square is extended once and EVERYTHING the proofs read stays in HBM:
 //   leaf slots      [W][W][96]            (level 0 of every row tree)
 //   row levels      level L: [W][W >> L][96]
+//   column levels   level L >= 1: [W columns][W >> L][96] (sample.hip: column-axis proofs)
 //   RFC levels      data-root tree over the 2W roots: level l: [2W >> l][32]
 // A proof is then index arithmetic on the host (which nodes: nmt
 // buildRangeProof's maximal subtrees outside the range, RFC aunts bottom-up)
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(256) void gather_kernel(const Piece* __restrict__ p
 // ResidentSquare
 // ---------------------------------------------------------------------------
 ResidentSquare::~ResidentSquare() {
-    for (DevBuf* b : {&eds, &levels, &col_a, &col_b, &roots_slots, &rfc, &rows, &cols, &root, &err, &scratch, &pieces})
+    for (DevBuf* b : {&eds, &levels, &col_levels, &roots_slots, &rfc, &rows, &cols, &root, &err, &scratch, &pieces})
         b->release();
 }
 
@@ -90,6 +91,13 @@ uint64_t ResidentSquare::level_offset(uint32_t L) const {   // bytes into `level
     const uint64_t W = 2ull * k;
     uint64_t off = 0;
     for (uint32_t l = 0; l < L; l++) off += W * (W >> l) * kSlot;
+    return off;
+}
+
+uint64_t ResidentSquare::col_level_offset(uint32_t L) const {   // bytes into `col_levels`, L >= 1
+    const uint64_t W = 2ull * k;
+    uint64_t off = 0;
+    for (uint32_t l = 1; l < L; l++) off += W * (W >> l) * kSlot;
     return off;
 }
 
@@ -105,8 +113,7 @@ int Engine::square_create(const uint8_t* ods, uint32_t k, ResidentSquare* sq) {
     int rc;
     if ((rc = check(sq->eds.ensure(eds_b), "hipMalloc"))) return rc;
     if ((rc = check(sq->levels.ensure(sq->level_offset(logW + 1)), "hipMalloc"))) return rc;
-    if ((rc = check(sq->col_a.ensure((size_t)W * W / 2 * kSlot), "hipMalloc"))) return rc;
-    if ((rc = check(sq->col_b.ensure((size_t)W * W / 2 * kSlot), "hipMalloc"))) return rc;
+    if ((rc = check(sq->col_levels.ensure(sq->col_level_offset(logW + 1)), "hipMalloc"))) return rc;
     if ((rc = check(sq->roots_slots.ensure((size_t)2 * W * kSlot), "hipMalloc"))) return rc;
     if ((rc = check(sq->rfc.ensure((size_t)2 * (2 * W) * 32), "hipMalloc"))) return rc;
     if ((rc = check(sq->rows.ensure((size_t)W * kNode), "hipMalloc"))) return rc;
@@ -120,15 +127,14 @@ int Engine::square_create(const uint8_t* ods, uint32_t k, ResidentSquare* sq) {
     uint8_t* lv = sq->levels.as<uint8_t>();
     const CellGrid g{sq->eds.as<uint8_t>(), 0, W, W, W, 0, 0, k};
     if ((rc = check(launch_leaves(g, 1, lv, sq->err.as<uint32_t>(), true, true, s), "leaf hashing"))) return rc;
-    // row forest: every level retained; column forest: ping-pong scratch
+    // both forests: every level retained (the columns' for the column-axis sample proofs, sample.hip)
     Forest f[2]{};
     f[0] = Forest{lv, 0, W, W, 1, nullptr, 0, sq->rows.as<uint8_t>(), 0, sq->roots_slots.as<uint8_t>(), 0, 0};
     f[1] = Forest{lv, 0, W, 1, W, nullptr, 0, sq->cols.as<uint8_t>(), 0, sq->roots_slots.as<uint8_t>(), 0, W};
-    uint8_t* colbuf[2] = {sq->col_a.as<uint8_t>(), sq->col_b.as<uint8_t>()};
     uint32_t L = 1;
     for (uint32_t m = W; m >= 2; m /= 2, L++) {
         f[0].out = lv + sq->level_offset(L);
-        f[1].out = colbuf[L & 1];
+        f[1].out = sq->col_levels.as<uint8_t>() + sq->col_level_offset(L);
         if ((rc = check(launch_level(f, 2, m, 1, s), "nmt level"))) return rc;
         for (int i = 0; i < 2; i++) {
             f[i].in = f[i].out;

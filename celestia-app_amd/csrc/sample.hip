@@ -1,0 +1,305 @@
+// sample.hip -- data-availability samples of a resident square: a batch of
+// (row, column, axis) cells of the EDS, each with its NMT inclusion proof
+// against the row or the column root and the merkle proof of that root against
+// the data root, answered by ONE launch from the nodes square_create keeps
+// (proof.hip), and the host side of checking such samples (the batch goes
+// through Engine::share_proofs_verify, verify.hip).
+//
+// Proof shape.  The axis trees are perfect trees of W = 2k leaves, so nmt
+// ProveRange(p, p + 1) always has D = log2 W nodes, one sibling per level:
+// node (p >> L) ^ 1 of level L.  nmt orders them depth first, left to right:
+// the left siblings top-down (L from D - 1 down to 0 where bit L of p is set),
+// then the right siblings bottom-up (L from 0 up to D - 1 where bit L is
+// clear).  The sibling of level L therefore goes to proof position
+//     bit L set:    popcount(p >> (L + 1))
+//     bit L clear:  popcount(p) + L - popcount(p & ((1 << L) - 1)).
+// The merkle proof of the root among rowRoots || colRoots (Total 4k = 2W) has
+// A = D + 1 aunts, bottom-up: digest ((idx >> l) ^ 1) of RFC level l.
+//
+// Mapping.  One wavefront per sample, four samples per workgroup.  A sample is
+// 512 + 29 + 90 D + 90 + 32 (A + 1) bytes of output (about 1.7 KiB at k = 128)
+// from D + A + 3 scattered places, so the work is latency and store bound, not
+// arithmetic: a wave gives every sample 64 independent 16-byte loads in flight
+// and keeps all its control flow (axis, level, bit tests) uniform.  The 90-byte
+// packed nodes start at any even address; the wave first puts the D + 1 slots
+// (16-byte loads, proof order) into LDS and then writes the packed bytes with
+// one aligned 4-byte store per lane, consecutive lanes on consecutive words
+// (256 B per wave instruction), the at most three bytes at either end of a
+// region singly.  Shares and digests are aligned and go out directly.
+// Every index the kernel uses was validated on the host
+// (Engine::square_sample_proofs).
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/cda.h"
+#include "engine.h"
+#include "sha256_dev.h"
+
+namespace cda {
+
+namespace {
+
+constexpr uint32_t kSampleWaves = 4;      // samples per workgroup
+constexpr uint32_t kSampleMaxD = 11;      // log2(2 * 1024)
+constexpr uint32_t kSampleSlots = kSampleMaxD + 2;   // proof nodes, the axis root, the namespace
+
+struct SampleArgs {
+    const uint32_t* coords;     // n words: row | col << 12 | axis << 24
+    uint32_t n, k, log_w;
+    const uint8_t* eds;         // [W][W][512]
+    const uint8_t* levels;      // row levels, level 0 = the leaf slots
+    const uint8_t* col_levels;  // column levels 1..
+    const uint8_t* root_slots;  // [2W][96]: row roots, then column roots
+    const uint32_t* rfc;        // RFC-6962 levels of the data-root tree, state words
+    uint8_t* shares;            // any output may be NULL
+    uint8_t* namespaces;
+    uint8_t* nodes;
+    uint8_t* roots;
+    uint8_t* leaf_hash;
+    uint8_t* aunts;
+};
+
+// bytes into `levels` / `col_levels` of level L (ResidentSquare::level_offset / col_level_offset)
+__device__ __forceinline__ uint64_t dev_level_offset(uint32_t W, uint32_t L, uint32_t first) {
+    uint64_t off = 0;
+    for (uint32_t l = first; l < L; l++) off += (uint64_t)W * (W >> l) * kSlot;
+    return off;
+}
+
+// `count` items of ITEM bytes, held in LDS at a stride of kSlot bytes, to the
+// packed bytes dst[0 : count * ITEM) at any address: whole aligned words by one
+// 4-byte store per lane, the bytes of a word that the region only partly covers
+// singly (a neighbouring sample owns the rest of that word).
+template <uint32_t ITEM>
+__device__ __forceinline__ void store_packed(const uint8_t* lds, uint32_t count, uint8_t* dst, uint32_t lane) {
+    const uint32_t len = count * ITEM;
+    const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u);
+    const uint32_t n_words = (a + len + 3) / 4;
+    for (uint32_t w = lane; w < n_words; w += 64) {
+        const int32_t b0 = (int32_t)(4 * w) - (int32_t)a;
+        uint32_t v = 0;
+        bool full = true;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int32_t b = b0 + t;
+            if (b >= 0 && b < (int32_t)len) {
+                const uint32_t item = (uint32_t)b / ITEM, o = (uint32_t)b % ITEM;
+                v |= (uint32_t)lds[item * kSlot + o] << (8 * t);
+            } else {
+                full = false;
+            }
+        }
+        if (full) {
+            *reinterpret_cast<uint32_t*>(dst + b0) = v;
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int32_t b = b0 + t;
+                if (b >= 0 && b < (int32_t)len) dst[b] = (uint8_t)(v >> (8 * t));
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64 * kSampleWaves) void sample_kernel(const SampleArgs a) {
+    __shared__ uint4 stage[kSampleWaves][kSampleSlots * (kSlot / 16)];
+    const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+    const uint32_t i = blockIdx.x * kSampleWaves + wave;
+    const bool live = i < a.n;   // uniform over the wave; no early return: the workgroup meets at the barrier
+    const uint32_t W = 2 * a.k, D = a.log_w, A = D + 1;
+    uint32_t row = 0, col = 0, axis = 0;
+    if (live) {
+        const uint32_t c = a.coords[i];
+        row = c & 0xFFFu;
+        col = (c >> 12) & 0xFFFu;
+        axis = c >> 24;
+    }
+    const uint32_t p = axis ? row : col;      // leaf position in the axis tree
+    const uint32_t tree = axis ? col : row;   // which tree of the axis
+    const uint64_t cell = (uint64_t)row * W + col;
+    uint4* st = stage[wave];
+    if (live) {
+        // the share: 32 lanes x 16 bytes; its first two words also give the Q0 namespace
+        uint4 sh = make_uint4(0, 0, 0, 0);
+        if (lane < 32) sh = reinterpret_cast<const uint4*>(a.eds + cell * kShare)[lane];
+        if (a.shares && lane < 32) reinterpret_cast<uint4*>(a.shares + (uint64_t)i * kShare)[lane] = sh;
+        if (lane < 2) {
+            const bool q0 = row < a.k && col < a.k;   // else ParitySharesNamespace: 29 bytes of 0xFF
+            st[(D + 1) * (kSlot / 16) + lane] = q0 ? sh : make_uint4(~0u, ~0u, ~0u, ~0u);
+        }
+        // the D siblings in proof order, then the axis root: six 16-byte loads per slot
+        for (uint32_t q = lane; q < (D + 1) * (kSlot / 16); q += 64) {
+            const uint32_t L = q / (kSlot / 16), part = q % (kSlot / 16);
+            const uint8_t* src;
+            uint32_t j;
+            if (L == D) {
+                src = a.root_slots + (uint64_t)(axis * W + tree) * kSlot;
+                j = D;
+            } else {
+                const uint32_t sib = (p >> L) ^ 1u;
+                if (L == 0)   // the leaf level: shared by both axes, a column reads it with stride W
+                    src = a.levels + (axis ? (uint64_t)sib * W + tree : (uint64_t)tree * W + sib) * kSlot;
+                else if (axis)
+                    src = a.col_levels + dev_level_offset(W, L, 1) + ((uint64_t)tree * (W >> L) + sib) * kSlot;
+                else
+                    src = a.levels + dev_level_offset(W, L, 0) + ((uint64_t)tree * (W >> L) + sib) * kSlot;
+                j = ((p >> L) & 1u) ? (uint32_t)__popc(p >> (L + 1))
+                                    : (uint32_t)__popc(p) + L - (uint32_t)__popc(p & ((1u << L) - 1u));
+            }
+            st[j * (kSlot / 16) + part] = reinterpret_cast<const uint4*>(src)[part];
+        }
+        // leaf hash and aunts: state words out as big-endian bytes, one word per lane
+        const uint32_t idx = axis * W + tree, T = 2 * W;   // Index among the Total = 4k roots
+        for (uint32_t q = lane; q < (A + 1) * 8; q += 64) {
+            const uint32_t item = q / 8, word = q % 8;
+            if (item == 0) {
+                if (a.leaf_hash)
+                    reinterpret_cast<uint32_t*>(a.leaf_hash + (uint64_t)i * 32)[word] = bswap32(a.rfc[(uint64_t)idx * 8 + word]);
+            } else if (a.aunts) {
+                const uint32_t l = item - 1;
+                const uint64_t entry = (uint64_t)(2 * T - ((2 * T) >> l)) + ((idx >> l) ^ 1u);
+                reinterpret_cast<uint32_t*>(a.aunts + ((uint64_t)i * A + l) * 32)[word] = bswap32(a.rfc[entry * 8 + word]);
+            }
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    const uint8_t* sb = reinterpret_cast<const uint8_t*>(st);
+    if (a.nodes) store_packed<kNode>(sb, D, a.nodes + (uint64_t)i * D * kNode, lane);
+    if (a.roots) store_packed<kNode>(sb + D * kSlot, 1, a.roots + (uint64_t)i * kNode, lane);
+    if (a.namespaces) store_packed<kNs>(sb + (D + 1) * kSlot, 1, a.namespaces + (uint64_t)i * kNs, lane);
+}
+
+// The first bad coordinate of a batch ("" if none): the text names the sample and the field.
+std::string check_coords(const uint32_t* rows, const uint32_t* cols, const uint8_t* axes, uint32_t n, uint32_t W) {
+    auto at = [](uint32_t i, const char* field, uint32_t v) {
+        return "sample " + std::to_string(i) + ": " + field + " " + std::to_string(v);
+    };
+    for (uint32_t i = 0; i < n; i++) {
+        if (rows[i] >= W) return at(i, "row", rows[i]) + " is not below the EDS width " + std::to_string(W);
+        if (cols[i] >= W) return at(i, "col", cols[i]) + " is not below the EDS width " + std::to_string(W);
+        if (axes && axes[i] > 1) return at(i, "axis", axes[i]) + " is neither 0 (row) nor 1 (column)";
+    }
+    return "";
+}
+
+}  // namespace
+
+int Engine::square_sample_proofs(ResidentSquare* sq, const uint32_t* rows, const uint32_t* cols, const uint8_t* axes,
+                                 uint32_t n, const SampleOut& o) {
+    if (n == 0) return CDA_OK;
+    if (!rows || !cols) return fail(CDA_ERR_INVALID, "null buffer");
+    const uint32_t k = sq->k, W = 2 * k, D = sq->log_w, A = D + 1;
+    const std::string bad = check_coords(rows, cols, axes, n, W);
+    if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
+    std::vector<uint32_t> packed(n);
+    for (uint32_t i = 0; i < n; i++) packed[i] = rows[i] | (cols[i] << 12) | ((axes ? axes[i] : 0u) << 24);
+    // scratch: the packed coordinates, then one struct-of-arrays region per requested output, each at a
+    // 16-byte boundary
+    struct Region {
+        uint8_t* host;
+        size_t bytes, off;
+    };
+    size_t total = ((size_t)n * 4 + 15) & ~(size_t)15;
+    auto region = [&](uint8_t* host, size_t bytes) {
+        Region r{host, host ? bytes : 0, total};
+        total += (r.bytes + 15) & ~(size_t)15;
+        return r;
+    };
+    const Region r_sh = region(o.shares, (size_t)n * kShare), r_ns = region(o.namespaces, (size_t)n * kNs),
+                 r_nd = region(o.nmt_nodes, (size_t)n * D * kNode), r_rt = region(o.axis_roots, (size_t)n * kNode),
+                 r_lh = region(o.leaf_hash, (size_t)n * 32), r_au = region(o.aunts, (size_t)n * A * 32);
+    hipStream_t s = stream_;
+    int rc;
+    if ((rc = check(sq->scratch.ensure(total), "hipMalloc"))) return rc;
+    uint8_t* scr = sq->scratch.as<uint8_t>();
+    if ((rc = check(hipMemcpyAsync(scr, packed.data(), (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D samples")))
+        return rc;
+    auto dev = [&](const Region& r) -> uint8_t* { return r.host ? scr + r.off : nullptr; };
+    SampleArgs a{};
+    a.coords = reinterpret_cast<const uint32_t*>(scr);
+    a.n = n;
+    a.k = k;
+    a.log_w = D;
+    a.eds = sq->eds.as<uint8_t>();
+    a.levels = sq->levels.as<uint8_t>();
+    a.col_levels = sq->col_levels.as<uint8_t>();
+    a.root_slots = sq->roots_slots.as<uint8_t>();
+    a.rfc = sq->rfc.as<uint32_t>();
+    a.shares = dev(r_sh);
+    a.namespaces = dev(r_ns);
+    a.nodes = dev(r_nd);
+    a.roots = dev(r_rt);
+    a.leaf_hash = dev(r_lh);
+    a.aunts = dev(r_au);
+    hipLaunchKernelGGL(sample_kernel, dim3((n + kSampleWaves - 1) / kSampleWaves), dim3(64 * kSampleWaves), 0, s, a);
+    if ((rc = check(hipGetLastError(), "sample proofs"))) return rc;
+    for (const Region* r : {&r_sh, &r_ns, &r_nd, &r_rt, &r_lh, &r_au})
+        if (r->bytes &&
+            (rc = check(hipMemcpyAsync(r->host, scr + r->off, r->bytes, hipMemcpyDeviceToHost, s), "D2H samples")))
+            return rc;
+    // `packed` is pageable and the outputs are the caller's: complete before returning
+    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+}
+
+int Engine::sample_proofs_verify(uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
+                                 const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,
+                                 const uint8_t* nmt_nodes, const uint8_t* axis_roots, const uint8_t* leaf_hash,
+                                 const uint8_t* aunts, uint8_t* verdict) {
+    if (k == 0 || (k & (k - 1)) || k > 1024)
+        return fail(CDA_ERR_INVALID, "square width must be a power of two <= 1024");
+    if (n == 0) return CDA_OK;
+    if (!data_roots || !rows || !cols || !shares || !nmt_nodes || !axis_roots || !leaf_hash || !aunts || !verdict)
+        return fail(CDA_ERR_INVALID, "null buffer");
+    const uint32_t W = 2 * k;
+    uint32_t D = 0;
+    while ((1u << D) < W) D++;
+    const uint32_t A = D + 1;
+    const std::string bad = check_coords(rows, cols, axes, n, W);
+    if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
+    // Everything a prover could lie about is derived here from (row, col, axis): the leaf namespace, the
+    // leaf position and the merkle Index / Total.  One segment per proof, fixed strides.
+    std::vector<uint8_t> ns((size_t)n * kNs);
+    std::vector<uint32_t> seg_off(n + 1), node_off(n + 1), aunt_off(n + 1);
+    std::vector<int32_t> st(n), en(n);
+    std::vector<int64_t> total(n, 2ll * W), index(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t axis = axes ? axes[i] : 0u;
+        if (rows[i] < k && cols[i] < k) std::memcpy(&ns[(size_t)i * kNs], shares + (size_t)i * kShare, kNs);
+        else std::memset(&ns[(size_t)i * kNs], 0xFF, kNs);
+        const uint32_t p = axis ? rows[i] : cols[i];
+        st[i] = (int32_t)p;
+        en[i] = (int32_t)p + 1;
+        index[i] = axis ? (int64_t)W + cols[i] : (int64_t)rows[i];
+    }
+    for (uint32_t i = 0; i <= n; i++) {
+        seg_off[i] = i;
+        node_off[i] = i * D;
+        aunt_off[i] = i * A;
+    }
+    cda_share_proof_batch b{};
+    b.n_proofs = n;
+    b.ns_len = kNs;
+    b.share_len = kShare;
+    b.data_roots = data_roots;
+    b.namespaces = ns.data();
+    b.seg_off = seg_off.data();
+    b.nmt_start = st.data();
+    b.nmt_end = en.data();
+    b.node_off = node_off.data();
+    b.nodes = nmt_nodes;
+    b.n_nodes = n * D;
+    b.row_roots = axis_roots;
+    b.rfc_total = total.data();
+    b.rfc_index = index.data();
+    b.rfc_leaf_hash = leaf_hash;
+    b.aunt_off = aunt_off.data();
+    b.aunts = aunts;
+    b.n_aunts = n * A;
+    b.shares = shares;
+    b.n_shares = n;
+    return share_proofs_verify(&b, verdict);
+}
+
+}  // namespace cda

@@ -36,6 +36,12 @@
  *   cda_square_*           resident squares: proof.NewShareInclusionProofFromEDS
  *                          (pkg/proof/proof.go:77), inclusion.GetCommitment
  *                          (pkg/inclusion/get_commit.go:12)
+ *   cda_square_sample_proofs / cda_sample_proofs_verify
+ *                          data-availability sampling of a built EDS: any cell
+ *                          (parity included) with nmt ProveRange(p, p+1) of its
+ *                          row or column tree (rsmt2d / wrapper trees,
+ *                          pkg/wrapper/nmt_wrapper.go:55-129) and the merkle proof
+ *                          of that root in the DAH; batched, and the batch check
  *   cda_nmt_axis_root(s) / cda_nmt_prove_range
  *                          wrapper.NewErasuredNamespacedMerkleTree + Push +
  *                          Root / ProveRange (pkg/wrapper/nmt_wrapper.go:55-129)
@@ -437,6 +443,39 @@ int cda_square_blob_commitments(cda_square *sq, const uint32_t *starts, const ui
  * the cache's "did not find sub tree root: [...]" (root still receives the
  * leaf it reached); row >= 2k: "row exceeds range of cache: max %d got %d". */
 int cda_square_subtree_root(cda_square *sq, uint32_t row, const uint8_t *walk, uint32_t walk_len, uint8_t *root);
+
+/* ---- Data-availability samples: serve and check cells of the EDS ------------
+ * What a full node does with an EDS after building it: answer samples of any
+ * of its cells, parity included, each proved against the row or the column
+ * root.  The square also keeps every level of every column tree for this. */
+#define CDA_AXIS_ROW 0
+#define CDA_AXIS_COL 1
+/* n samples of the EDS of a resident square.  Sample i is cell (rows[i], cols[i]), 0 <= both < 2k, proved
+ * against the row root (axes[i] == 0) or the column root (1); axes == NULL means all rows.
+ * D = log2(2k) proof nodes and A = log2(4k) aunts per sample, fixed strides, any output may be NULL:
+ *   shares      n*512    the cell
+ *   namespaces  n*29     the leaf namespace: share[0:29] if row < k && col < k, else ParitySharesNamespace
+ *   nmt_nodes   n*D*90   nmt ProveRange(p, p+1) of the axis tree, p = col (row axis) or row (column axis):
+ *                        left siblings top-down, then right siblings bottom-up
+ *   axis_roots  n*90     the row / column root
+ *   leaf_hash   n*32, aunts n*A*32   merkle proof of that root among rowRoots || colRoots:
+ *                        Total 4k, Index = row (row axis) or 2k + col (column axis), aunts bottom-up
+ * Coordinates are checked on the host before anything is enqueued: CDA_ERR_INVALID naming the sample and
+ * the field, outputs untouched.  n == 0 returns CDA_OK.  One launch per call, whatever n; host buffers,
+ * complete when the call returns.  A square created with CDA_ERR_PUSH_ORDER serves samples like any other. */
+int cda_square_sample_proofs(cda_square *sq, const uint32_t *rows, const uint32_t *cols, const uint8_t *axes,
+                             uint32_t n, uint8_t *shares, uint8_t *namespaces, uint8_t *nmt_nodes,
+                             uint8_t *axis_roots, uint8_t *leaf_hash, uint8_t *aunts);
+/* The verifying side of cda_square_sample_proofs for a square of ODS width k: same arrays, plus one data
+ * root per sample (n*32).  The namespace, the leaf position and the merkle Index/Total are derived from
+ * (row, col, axis) here, never taken from the prover.  verdict[i]: 0 valid, 1 the axis root does not
+ * verify against the data root, 2 the cell does not verify against the axis root (1 wins).
+ * Coordinates out of range, or k not a power of two <= 1024: CDA_ERR_INVALID, verdict untouched.
+ * Cells with verdict 0 are what cda_repair's `present` mask is meant to be filled from. */
+int cda_sample_proofs_verify(cda_ctx *ctx, uint32_t k, uint32_t n, const uint8_t *data_roots,
+                             const uint32_t *rows, const uint32_t *cols, const uint8_t *axes,
+                             const uint8_t *shares, const uint8_t *nmt_nodes, const uint8_t *axis_roots,
+                             const uint8_t *leaf_hash, const uint8_t *aunts, uint8_t *verdict);
 
 /* ---- Repair ------------------------------------------
  * rsmt2d ExtendedDataSquare.Repair(rowRoots, colRoots) (EXT v0.14.0,
