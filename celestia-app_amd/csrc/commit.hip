@@ -52,18 +52,11 @@ using square::Tree;
 // Merkle leaves are hashed where the roots are produced, in parallel, instead
 // of on the per-blob serial path.
 __device__ __forceinline__ void store_rfc_leaf(const uint32_t (&I)[kSlotWords], uint32_t* __restrict__ dig) {
-    uint32_t w[16];
-    ShaState st;
-    sha_init(st);
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-#pragma unroll
-        for (int j = 0; j < 16; j++) w[j] = rfc_leaf_msg(I, 16 * q + j);
-        sha_compress(st, w);
-    }
+    uint32_t D[8];
+    rfc_leaf_u<false>(I, D, false);
     uint4* d = reinterpret_cast<uint4*>(dig);
-    d[0] = make_uint4(st.h[0], st.h[1], st.h[2], st.h[3]);
-    d[1] = make_uint4(st.h[4], st.h[5], st.h[6], st.h[7]);
+    d[0] = make_uint4(D[0], D[1], D[2], D[3]);
+    d[1] = make_uint4(D[4], D[5], D[6], D[7]);
 }
 
 // Per-leaf subtree index and the subtree list, built on the device from the
@@ -255,6 +248,8 @@ __global__ __launch_bounds__(256) void subtree_level_kernel(const Tree* __restri
     uint32_t L[kSlotWords], R[kSlotWords], w[16];
     load_slot_be(in + (size_t)(2 * n) * kSlot, L);
     load_slot_be(in + (size_t)(2 * n + 1) * kSlot, R);
+    // hash_node_u<false> (sha256_dev.h), written out: through the call this
+    // kernel is allocated 189 VGPRs instead of 123 (two waves per SIMD, not four)
     ShaState st;
     sha_init(st);
 #pragma unroll
@@ -274,20 +269,14 @@ __global__ __launch_bounds__(256) void subtree_level_kernel(const Tree* __restri
     }
 }
 
+// rfc_inner_plain from and to digest words in LDS.
 __device__ __forceinline__ void rfc_inner(const uint32_t* a, const uint32_t* b, uint32_t* o) {
-    uint32_t A[8], B[8], w[16];
+    uint32_t A[8], B[8], D[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) { A[j] = a[j]; B[j] = b[j]; }
-    ShaState st;
-    sha_init(st);
+    rfc_inner_plain(A, B, D);
 #pragma unroll
-    for (int q = 0; q < 2; q++) {
-#pragma unroll
-        for (int j = 0; j < 16; j++) w[j] = rfc_inner_msg(A, B, 16 * q + j);
-        sha_compress(st, w);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++) o[j] = st.h[j];
+    for (int j = 0; j < 8; j++) o[j] = D[j];
 }
 
 // One wave per blob: RFC-6962 root over its subtree roots' leaf digests (a
@@ -300,13 +289,13 @@ __global__ __launch_bounds__(64) void commitment_kernel(const uint32_t* __restri
     const uint32_t b = blockIdx.x;
     const uint32_t t0 = blob_tree0[b];
     uint32_t m = blob_tree0[b + 1] - t0;
-    uint32_t* o = reinterpret_cast<uint32_t*>(out + (size_t)b * 32);
+    uint8_t* o = out + (size_t)b * 32;
     if (m == 0) {   // no shares: merkle.HashFromByteSlices(nil) = sha256("")
         if (threadIdx.x == 0) {
             const uint32_t e[8] = {0x42c4b0e3u, 0x141cfc98u, 0xc8f4fb9au, 0x24b96f99u,
                                    0xe441ae27u, 0x4c939b64u, 0x1b9995a4u, 0x55b85278u};
 #pragma unroll
-            for (int j = 0; j < 8; j++) o[j] = e[j];
+            for (int j = 0; j < 8; j++) reinterpret_cast<uint32_t*>(o)[j] = e[j];
         }
         return;
     }
@@ -344,10 +333,7 @@ __global__ __launch_bounds__(64) void commitment_kernel(const uint32_t* __restri
         dst = t;
         m = pairs + (m & 1);
     }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < 8; j++) o[j] = bswap32(src[j]);
-    }
+    if (threadIdx.x == 0) store_digest_be(o, src);
 }
 
 // RFC-6962 levels of a group of G <= 64 consecutive blobs whose subtree-root

@@ -79,6 +79,7 @@ __device__ __forceinline__ void leaf_order_check(const CellGrid& g, const uint8_
 // next workgroup, and the own namespace waits in LDS: the launch's FETCH_SIZE
 // -5 %, WRITE_SIZE -20 % (its six spilled values gone, 128 -> 125 VGPRs), time
 // equal (VALU-bound; profiles/r05/leaf_ns_ab.txt).
+// leaf29_digest below streams the share the same way: edit the two together.
 __device__ __forceinline__ void leaf_cell(const CellGrid& g, uint8_t* __restrict__ slots, uint32_t* __restrict__ err,
                                           int check_rows, int check_cols, size_t sq, uint32_t r, uint32_t c,
                                           uint32_t* ns_slot) {
@@ -159,6 +160,55 @@ __device__ __forceinline__ void leaf_cell(const CellGrid& g, uint8_t* __restrict
     uint32_t out[kSlotWords];
     leaf_node_words(nsw, st.h, out);
     store_slot(slots + (sq * (size_t)g.rows * g.cols + cell) * kSlot, out);
+}
+
+// The 29-byte, 512-byte leaf digest sha256(0x00 || ns || share) for the proof
+// verifier (verify.hip): leaf_cell's streaming of the share (blocks 1-8 are
+// the same text: edit the two together) with the namespace given by the caller
+// instead of read from the share.
+// nsw: big-endian namespace words (byte 28 in the top byte of nsw[7]).
+__device__ __forceinline__ void leaf29_digest(const uint8_t* __restrict__ share, const uint32_t (&nsw)[8],
+                                              uint32_t (&d)[8]) {
+    const uint4* src = reinterpret_cast<const uint4*>(share);
+    ShaState st;
+    sha_init(st);
+    uint32_t cur[16], nxt[16], tail[8], w[16];
+    load_raw16(src, cur);
+    load_raw16(src + 4, nxt);
+    // block 0: 0x00 || ns(29) || share[0:34]
+    w[0] = nsw[0] >> 8;
+#pragma unroll
+    for (int i = 1; i < 7; i++) w[i] = funnel8(nsw[i - 1], nsw[i], 1);
+    w[7] = (nsw[6] << 24) | ((nsw[7] >> 24) << 16) | __builtin_amdgcn_perm(cur[0], cur[0], 0x0C0C0001u);
+#pragma unroll
+    for (int i = 8; i < 16; i++) w[i] = body_word(cur[i - 8], cur[i - 7]);
+    sha_compress(st, w);
+#pragma unroll
+    for (int i = 0; i < 8; i++) tail[i] = cur[8 + i];
+#pragma unroll 1
+    for (int b = 1; b < 8; b++) {
+#pragma unroll
+        for (int i = 0; i < 16; i++) cur[i] = nxt[i];
+        if (b < 7) load_raw16(src + 4 * (b + 1), nxt);
+#pragma unroll
+        for (int t = 0; t < 7; t++) w[t] = body_word(tail[t], tail[t + 1]);
+        w[7] = body_word(tail[7], cur[0]);
+#pragma unroll
+        for (int t = 8; t < 16; t++) w[t] = body_word(cur[t - 8], cur[t - 7]);
+#pragma unroll
+        for (int i = 0; i < 8; i++) tail[i] = cur[8 + i];
+        sha_compress(st, w);
+    }
+    // block 8: share words 120..127 then padding (542-B message)
+#pragma unroll
+    for (int t = 0; t < 7; t++) w[t] = body_word(tail[t], tail[t + 1]);
+    w[7] = __builtin_amdgcn_perm(tail[7], tail[7], 0x02030C0Cu) | 0x8000u;
+#pragma unroll
+    for (int t = 8; t < 15; t++) w[t] = 0;
+    w[15] = kLeafMsgBits;
+    sha_compress(st, w);
+#pragma unroll
+    for (int j = 0; j < 8; j++) d[j] = st.h[j];
 }
 
 }  // namespace cda

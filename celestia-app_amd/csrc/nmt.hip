@@ -787,46 +787,28 @@ __global__ __launch_bounds__(256) void data_root_kernel(const uint8_t* __restric
     extern __shared__ __attribute__((aligned(16))) uint32_t hs[];   // ping [n][8] | pong [n/2][8]
     const size_t sq = blockIdx.x;
     for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-        uint32_t I[kSlotWords], w[16];
+        uint32_t I[kSlotWords], D[8];
         load_slot_be(root_slots + (sq * n + i) * (size_t)kSlot, I);
-        ShaState st;
-        sha_init(st);
+        rfc_leaf_u<false>(I, D, false);
 #pragma unroll
-        for (int b = 0; b < 2; b++) {
-#pragma unroll
-            for (int j = 0; j < 16; j++) w[j] = rfc_leaf_msg(I, 16 * b + j);
-            sha_compress(st, w);
-        }
-#pragma unroll
-        for (int j = 0; j < 8; j++) hs[i * 8 + j] = st.h[j];
+        for (int j = 0; j < 8; j++) hs[i * 8 + j] = D[j];
     }
     __syncthreads();
     uint32_t* src = hs;
     uint32_t* dst = hs + n * 8;
     for (uint32_t m = n / 2; m >= 1; m >>= 1) {
         for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
-            uint32_t A[8], B[8], w[16];
+            uint32_t A[8], B[8], D[8];
 #pragma unroll
             for (int j = 0; j < 8; j++) { A[j] = src[(2 * i) * 8 + j]; B[j] = src[(2 * i + 1) * 8 + j]; }
-            ShaState st;
-            sha_init(st);
+            rfc_inner_plain(A, B, D);
 #pragma unroll
-            for (int b = 0; b < 2; b++) {
-#pragma unroll
-                for (int j = 0; j < 16; j++) w[j] = rfc_inner_msg(A, B, 16 * b + j);
-                sha_compress(st, w);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j++) dst[i * 8 + j] = st.h[j];
+            for (int j = 0; j < 8; j++) dst[i * 8 + j] = D[j];
         }
         __syncthreads();
         uint32_t* t = src; src = dst; dst = t;
     }
-    if (threadIdx.x == 0) {
-        uint32_t* o = reinterpret_cast<uint32_t*>(data_roots + sq * 32);
-#pragma unroll
-        for (int j = 0; j < 8; j++) o[j] = bswap32(src[j]);
-    }
+    if (threadIdx.x == 0) store_digest_be(data_roots + sq * 32, src);
 }
 
 // RFC-6962 leaf digests sha256(0x00 || root) of n 96-B root slots (one thread
@@ -835,19 +817,12 @@ __global__ __launch_bounds__(256) void rfc_leaf_kernel(const uint8_t* __restrict
                                                       uint32_t* __restrict__ dig) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    uint32_t I[kSlotWords], w[16];
+    uint32_t I[kSlotWords], D[8];
     load_slot_be(slots + (size_t)i * kSlot, I);
-    ShaState st;
-    sha_init(st);
-#pragma unroll
-    for (int b = 0; b < 2; b++) {
-#pragma unroll
-        for (int j = 0; j < 16; j++) w[j] = rfc_leaf_msg(I, 16 * b + j);
-        sha_compress(st, w);
-    }
+    rfc_leaf_u<false>(I, D, false);
     uint4* d = reinterpret_cast<uint4*>(dig + (size_t)i * 8);
-    d[0] = make_uint4(st.h[0], st.h[1], st.h[2], st.h[3]);
-    d[1] = make_uint4(st.h[4], st.h[5], st.h[6], st.h[7]);
+    d[0] = make_uint4(D[0], D[1], D[2], D[3]);
+    d[1] = make_uint4(D[4], D[5], D[6], D[7]);
 }
 
 __global__ __launch_bounds__(512) void data_root_digest_kernel(const uint32_t* __restrict__ dig, uint32_t n,

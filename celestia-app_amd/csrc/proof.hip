@@ -23,12 +23,11 @@
 #include "../../include/cda.h"
 #include "engine.h"
 #include "sha256_dev.h"
+#include "tree_index.h"
 
 namespace cda {
 
 namespace {
-
-bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
 
 // All RFC-6962 levels of the data-root tree (n leaf digests, n a power of two)
 // in one workgroup: level 0 = the leaf digests, level l has n >> l entries.
@@ -38,19 +37,12 @@ __global__ __launch_bounds__(1024) void rfc_levels_kernel(uint32_t* __restrict__
     for (uint32_t m = n / 2; m >= 1; m >>= 1) {
         uint32_t* dst = src + 2 * m * 8;
         for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
-            uint32_t A[8], B[8], w[16];
+            uint32_t A[8], B[8], D[8];
 #pragma unroll
             for (int j = 0; j < 8; j++) { A[j] = src[16 * i + j]; B[j] = src[16 * i + 8 + j]; }
-            ShaState st;
-            sha_init(st);
+            rfc_inner_plain(A, B, D);
 #pragma unroll
-            for (int q = 0; q < 2; q++) {
-#pragma unroll
-                for (int j = 0; j < 16; j++) w[j] = rfc_inner_msg(A, B, 16 * q + j);
-                sha_compress(st, w);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; j++) dst[8 * i + j] = st.h[j];
+            for (int j = 0; j < 8; j++) dst[8 * i + j] = D[j];
         }
         __syncthreads();
         src = dst;
@@ -88,24 +80,16 @@ ResidentSquare::~ResidentSquare() {
 }
 
 uint64_t ResidentSquare::level_offset(uint32_t L) const {   // bytes into `levels`
-    const uint64_t W = 2ull * k;
-    uint64_t off = 0;
-    for (uint32_t l = 0; l < L; l++) off += W * (W >> l) * kSlot;
-    return off;
+    return cda::level_offset(2 * k, L, 0, kSlot);
 }
 
 uint64_t ResidentSquare::col_level_offset(uint32_t L) const {   // bytes into `col_levels`, L >= 1
-    const uint64_t W = 2ull * k;
-    uint64_t off = 0;
-    for (uint32_t l = 1; l < L; l++) off += W * (W >> l) * kSlot;
-    return off;
+    return cda::level_offset(2 * k, L, 1, kSlot);
 }
 
 int Engine::square_create(const uint8_t* ods, uint32_t k, ResidentSquare* sq) {
     if (!is_pow2(k) || k > 1024) return fail(CDA_ERR_INVALID, "square width must be a power of two <= 1024");
-    const uint32_t W = 2 * k;
-    uint32_t logW = 0;
-    while ((1u << logW) < W) logW++;
+    const uint32_t W = 2 * k, logW = ceil_log2(W);
     sq->k = k;
     sq->log_w = logW;
     const size_t ods_b = (size_t)k * k * kShare, eds_b = (size_t)W * W * kShare;
@@ -205,36 +189,12 @@ int Engine::square_gather_device(ResidentSquare* sq, const std::vector<GatherPie
 // ---------------------------------------------------------------------------
 // Share inclusion proof (pkg/proof/proof.go:77-206)
 // ---------------------------------------------------------------------------
-namespace {
-
-// nmt buildRangeProof on a perfect tree of `width` leaves: the maximal
-// subtrees outside [s, e), depth-first, left to right, as (level, index).
-void range_proof_nodes(uint32_t lo, uint32_t hi, uint32_t s, uint32_t e, uint32_t level,
-                       std::vector<std::pair<uint32_t, uint32_t>>& out) {
-    if (hi <= s || lo >= e) {
-        out.emplace_back(level, lo >> level);
-        return;
-    }
-    if (hi - lo == 1) return;   // a leaf inside the range
-    const uint32_t mid = (lo + hi) / 2;
-    range_proof_nodes(lo, mid, s, e, level - 1, out);
-    range_proof_nodes(mid, hi, s, e, level - 1, out);
-}
-
-uint32_t log2u(uint32_t x) {
-    uint32_t l = 0;
-    while ((1u << l) < x) l++;
-    return l;
-}
-
-}  // namespace
-
 int Engine::square_share_proof(ResidentSquare* sq, uint32_t start, uint32_t end, ShareProofOut* o) {
     const uint32_t k = sq->k, W = 2 * k, logW = sq->log_w;
     if (start >= end || end > k * k) return fail(CDA_ERR_INVALID, "share range out of the original square");
     const uint32_t startRow = start / k, endRow = (end - 1) / k;
     const uint32_t startLeaf = start % k, endLeaf = (end - 1) % k;
-    const uint32_t nrows = endRow - startRow + 1, maxn = 2 * logW, naunts = log2u(2 * W);
+    const uint32_t nrows = endRow - startRow + 1, maxn = 2 * logW, naunts = ceil_log2(2 * W);
     // staging layout: shares | nodes [nrows][maxn][90] | roots [nrows][90] | leaf hash [nrows][32] | aunts
     const size_t sh_b = (size_t)(end - start) * kShare;
     const size_t nd_off = sh_b, rt_off = nd_off + (size_t)nrows * maxn * kNode;
@@ -254,7 +214,7 @@ int Engine::square_share_proof(ResidentSquare* sq, uint32_t start, uint32_t end,
         pieces.push_back(GatherPiece{GatherPiece::kEds, ((uint64_t)r * W + s0) * kShare, sh_at, (e0 - s0) * kShare});
         sh_at += (size_t)(e0 - s0) * kShare;
         std::vector<std::pair<uint32_t, uint32_t>> nodes;
-        range_proof_nodes(0, W, s0, e0, logW, nodes);
+        prove_nodes(0, W, s0, e0, nodes);
         o->nmt_count[i] = (uint32_t)nodes.size();
         for (size_t q = 0; q < nodes.size(); q++) {
             const uint32_t L = nodes[q].first, p = nodes[q].second;
@@ -364,7 +324,7 @@ int Engine::square_blob_commitments(ResidentSquare* sq, const uint32_t* starts, 
     if (n == 0) return CDA_OK;
     if (threshold == 0) return fail(CDA_ERR_INVALID, "subtree root threshold must be positive");
     const uint32_t k = sq->k, W = 2 * k;
-    const int maxDepth = (int)log2u(k);
+    const int maxDepth = (int)ceil_log2(k);
     std::vector<GatherPiece> pieces;
     std::vector<uint32_t> bt{0};
     uint32_t max_n = 0;
@@ -378,7 +338,7 @@ int Engine::square_blob_commitments(ResidentSquare* sq, const uint32_t* starts, 
             return fail(CDA_ERR_INVALID, "cannot get commitment for blob that doesn't fit in square");
         const uint32_t startRow = (uint32_t)(start / k), endRow = (uint32_t)((start + len - 1) / k);
         const int nsi = (int)(start % k), nei = (int)(start + len - (uint64_t)endRow * k);
-        const int minDepth = maxDepth - (int)log2u(w);
+        const int minDepth = maxDepth - (int)ceil_log2(w);
         uint32_t cnt = 0;
         for (uint32_t r = startRow; r <= endRow; r++) {
             const int s0 = r == startRow ? nsi : 0, e0 = r == endRow ? nei : (int)k;

@@ -35,6 +35,7 @@
 #include "../../include/cda.h"
 #include "engine.h"
 #include "sha256_dev.h"
+#include "tree_index.h"
 
 namespace cda {
 
@@ -59,13 +60,6 @@ struct SampleArgs {
     uint8_t* leaf_hash;
     uint8_t* aunts;
 };
-
-// bytes into `levels` / `col_levels` of level L (ResidentSquare::level_offset / col_level_offset)
-__device__ __forceinline__ uint64_t dev_level_offset(uint32_t W, uint32_t L, uint32_t first) {
-    uint64_t off = 0;
-    for (uint32_t l = first; l < L; l++) off += (uint64_t)W * (W >> l) * kSlot;
-    return off;
-}
 
 // `count` items of ITEM bytes, held in LDS at a stride of kSlot bytes, to the
 // packed bytes dst[0 : count * ITEM) at any address: whole aligned words by one
@@ -141,9 +135,9 @@ __global__ __launch_bounds__(64 * kSampleWaves) void sample_kernel(const SampleA
                 if (L == 0)   // the leaf level: shared by both axes, a column reads it with stride W
                     src = a.levels + (axis ? (uint64_t)sib * W + tree : (uint64_t)tree * W + sib) * kSlot;
                 else if (axis)
-                    src = a.col_levels + dev_level_offset(W, L, 1) + ((uint64_t)tree * (W >> L) + sib) * kSlot;
+                    src = a.col_levels + level_offset(W, L, 1, kSlot) + ((uint64_t)tree * (W >> L) + sib) * kSlot;
                 else
-                    src = a.levels + dev_level_offset(W, L, 0) + ((uint64_t)tree * (W >> L) + sib) * kSlot;
+                    src = a.levels + level_offset(W, L, 0, kSlot) + ((uint64_t)tree * (W >> L) + sib) * kSlot;
                 j = ((p >> L) & 1u) ? (uint32_t)__popc(p >> (L + 1))
                                     : (uint32_t)__popc(p) + L - (uint32_t)__popc(p & ((1u << L) - 1u));
             }

@@ -428,6 +428,56 @@ CDA_HD void rfc_leaf_u(const uint32_t (&I)[kSlotWords], uint32_t (&D)[8], bool A
     }
     h.digest(A, D);
 }
+// RFC-6962 inner digest sha256(0x01 || a || b) of two digests, both blocks
+// through the message schedule: the throughput-bound kernels (a thread per
+// node, many nodes).  rfc_inner_u below runs block 1 from a table instead.
+CDA_HD void rfc_inner_plain(const uint32_t (&a)[8], const uint32_t (&b)[8], uint32_t (&D)[8]) {
+    ShaState st;
+    sha_init(st);
+    uint32_t w[16];
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+#pragma unroll
+        for (int j = 0; j < 16; j++) w[j] = rfc_inner_msg(a, b, 16 * q + j);
+        sha_compress(st, w);
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) D[j] = st.h[j];
+}
+
+// ---------------------------------------------------------------------------
+// Digest and packed-node byte I/O (digests are kept as eight big-endian-valued
+// state words; on the wire they are 32 bytes).
+// ---------------------------------------------------------------------------
+CDA_HD void store_digest_bytes(uint8_t* o, const uint32_t (&d)[8]) {
+    for (int j = 0; j < 8; j++) {
+        o[4 * j + 0] = (uint8_t)(d[j] >> 24);
+        o[4 * j + 1] = (uint8_t)(d[j] >> 16);
+        o[4 * j + 2] = (uint8_t)(d[j] >> 8);
+        o[4 * j + 3] = (uint8_t)d[j];
+    }
+}
+// Eight state words to 32 bytes at a 4-byte aligned address.
+CDA_HD void store_digest_be(uint8_t* o, const uint32_t* d) {
+    uint32_t* q = reinterpret_cast<uint32_t*>(o);
+#pragma unroll
+    for (int j = 0; j < 8; j++) q[j] = bswap32(d[j]);
+}
+// Big-endian words of 32 bytes at a 4-byte aligned address.
+CDA_HD void load_digest_be(const uint8_t* p, uint32_t (&d)[8]) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+    for (int j = 0; j < 8; j++) d[j] = bswap32(q[j]);
+}
+// Big-endian slot words of a packed 90-B node at any byte address.
+CDA_HD void load_packed_be(const uint8_t* p, uint32_t (&w)[kSlotWords]) {
+#pragma unroll
+    for (int t = 0; t < 22; t++)
+        w[t] = ((uint32_t)p[4 * t] << 24) | ((uint32_t)p[4 * t + 1] << 16) | ((uint32_t)p[4 * t + 2] << 8) | p[4 * t + 3];
+    w[22] = ((uint32_t)p[88] << 24) | ((uint32_t)p[89] << 16);
+    w[23] = 0;
+}
+
 // ---------------------------------------------------------------------------
 // RFC-6962 inner node, second block.  The 65-B message 0x01 || a || b leaves
 // one data byte in block 1: b[31] || 0x80 || 0 ... || 520 (bits).  Its whole

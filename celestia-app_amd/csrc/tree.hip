@@ -24,64 +24,13 @@
 
 #include "../../include/cda.h"
 #include "engine.h"
-#include "sha256_dev.h"
+#include "leaf_dev.h"
+#include "sha_bytes_dev.h"
+#include "tree_index.h"
 
 namespace cda {
 
 namespace {
-
-// SHA-256 of pre[0:npre] || data[0:len] (npre <= 32), big-endian state words.
-__device__ void sha_generic(const uint8_t (&pre)[32], uint32_t npre, const uint8_t* __restrict__ data, uint64_t len,
-                            uint32_t (&out)[8]) {
-    ShaState st;
-    sha_init(st);
-    const uint64_t total = npre + len;
-    const uint64_t n_blocks = (total + 9 + 63) / 64;
-    auto byte_at = [&](uint64_t i) -> uint32_t {
-        if (i < npre) return pre[i];
-        if (i < total) return data[i - npre];
-        if (i == total) return 0x80u;
-        return 0;
-    };
-    const uint64_t bits = total * 8;
-    for (uint64_t b = 0; b < n_blocks; b++) {
-        uint32_t w[16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const uint64_t p = b * 64 + 4 * j;
-            w[j] = (byte_at(p) << 24) | (byte_at(p + 1) << 16) | (byte_at(p + 2) << 8) | byte_at(p + 3);
-        }
-        if (b == n_blocks - 1) {
-            w[14] = (uint32_t)(bits >> 32);
-            w[15] = (uint32_t)bits;
-        }
-        sha_compress(st, w);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++) out[j] = st.h[j];
-}
-
-// Big-endian namespace words of a cell (byte 28 in the top byte of word 7).
-__device__ void ns_words(const uint8_t* cell, bool parity, uint32_t (&ns)[8]) {
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        uint32_t v = 0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int i = 4 * j + q;
-            const uint32_t byte = parity ? 0xFFu : (i < kNs ? cell[i] : 0u);
-            v |= (i < kNs ? byte : 0u) << (24 - 8 * q);
-        }
-        ns[j] = v;
-    }
-}
-
-__device__ __forceinline__ bool ns_less_w(const uint32_t (&a)[8], const uint32_t (&b)[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-        if (a[i] != b[i]) return a[i] < b[i];
-    return false;
-}
 
 // One leaf per (tree, push): slot = ns || ns || sha256(0x00 || ns || cell).
 // err[t] = min push position whose namespace is below the previous one.
@@ -96,21 +45,19 @@ __global__ __launch_bounds__(256) void gen_leaf_kernel(const uint8_t* __restrict
     const uint8_t* cell = cells + id * cell_len;
     const bool parity = !(i < square_size && ax < square_size);   // isQuadrantZero
     uint32_t ns[8];
-    ns_words(cell, parity, ns);
-    uint8_t pre[32];
-    pre[0] = 0x00;
+    load_ns_bytes(cell, parity, ns);
+    uint8_t nsb[kNs];
 #pragma unroll
-    for (int j = 0; j < kNs; j++) pre[1 + j] = (uint8_t)(ns[j / 4] >> (24 - 8 * (j % 4)));
-    pre[30] = pre[31] = 0;
+    for (int j = 0; j < kNs; j++) nsb[j] = (uint8_t)(ns[j / 4] >> (24 - 8 * (j % 4)));
     uint32_t d[8];
-    sha_generic(pre, 1 + kNs, cell, cell_len, d);
+    sha_cat(0x00, nsb, kNs, cell, cell_len, d);
     uint32_t out[kSlotWords];
     leaf_node_words(ns, d, out);
     store_slot(slots + id * kSlot, out);
     if (i > 0) {
         uint32_t prev[8];
-        ns_words(cell - cell_len, !((i - 1) < square_size && ax < square_size), prev);
-        if (ns_less_w(ns, prev)) atomicMin(err + t, i);
+        load_ns_bytes(cell - cell_len, !((i - 1) < square_size && ax < square_size), prev);
+        if (ns_less(ns, prev)) atomicMin(err + t, i);
     }
 }
 
@@ -132,19 +79,10 @@ __global__ __launch_bounds__(256) void gen_level_kernel(const uint8_t* __restric
         for (int q = 0; q < 6; q++) d[q] = s[q];
         return;
     }
-    uint32_t L[kSlotWords], R[kSlotWords], w[16];
+    uint32_t L[kSlotWords], R[kSlotWords], ow[kSlotWords];
     load_slot_be(l, L);
     load_slot_be(l + kSlot, R);
-    ShaState st;
-    sha_init(st);
-#pragma unroll
-    for (int b = 0; b < 3; b++) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) w[i] = node_msg(L, R, 16 * b + i);
-        sha_compress(st, w);
-    }
-    uint32_t ow[kSlotWords];
-    inner_node_words(L, R, st.h, ow);
+    hash_node_u<false>(L, R, ow, false);
     store_slot(o, ow);
 }
 
@@ -154,9 +92,8 @@ __global__ __launch_bounds__(256) void gen_rfc_leaf_kernel(const uint8_t* __rest
                                                           uint32_t* __restrict__ dig) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    uint8_t pre[32] = {0};
     uint32_t d[8];
-    sha_generic(pre, 1, items + off[i], off[i + 1] - off[i], d);
+    sha_cat(0x00, items + off[i], off[i + 1] - off[i], nullptr, 0, d);
 #pragma unroll
     for (int j = 0; j < 8; j++) dig[(size_t)i * 8 + j] = d[j];
 }
@@ -173,19 +110,10 @@ __global__ __launch_bounds__(256) void gen_rfc_levels_kernel(uint32_t* __restric
             const uint32_t p = base + threadIdx.x;
             uint32_t h[8];
             if (p < half) {
-                uint32_t A[8], B[8], w[16];
+                uint32_t A[8], B[8];
 #pragma unroll
                 for (int j = 0; j < 8; j++) { A[j] = dig[(2 * p) * 8 + j]; B[j] = dig[(2 * p + 1) * 8 + j]; }
-                ShaState st;
-                sha_init(st);
-#pragma unroll
-                for (int b = 0; b < 2; b++) {
-#pragma unroll
-                    for (int j = 0; j < 16; j++) w[j] = rfc_inner_msg(A, B, 16 * b + j);
-                    sha_compress(st, w);
-                }
-#pragma unroll
-                for (int j = 0; j < 8; j++) h[j] = st.h[j];
+                rfc_inner_plain(A, B, h);
             }
             __syncthreads();
             if (p < half) {
@@ -225,31 +153,6 @@ const uint8_t kEmptyRoot[kNode] = {
     0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
     0xe3, 0xb0, 0xc4, 0x42, 0x98, 0xfc, 0x1c, 0x14, 0x9a, 0xfb, 0xf4, 0xc8, 0x99, 0x6f, 0xb9, 0x24,
     0x27, 0xae, 0x41, 0xe4, 0x64, 0x9b, 0x93, 0x4c, 0xa4, 0x95, 0x99, 0x1b, 0x78, 0x52, 0xb8, 0x55};
-
-bool is_pow2(uint64_t x) { return x && !(x & (x - 1)); }
-
-// Level sizes of the promoted-pairing tree over n leaves: n, ceil(n/2), ..., 1.
-std::vector<uint32_t> level_counts(uint32_t n) {
-    std::vector<uint32_t> c{n};
-    while (c.back() > 1) c.push_back((c.back() + 1) / 2);
-    return c;
-}
-
-// nmt ProveRange node order: maximal subtrees outside [start, end), depth
-// first, left to right, as (level, index) of the promoted-pairing tree.
-void prove_nodes(uint32_t lo, uint32_t hi, uint32_t start, uint32_t end, std::vector<std::pair<uint32_t, uint32_t>>& out) {
-    if (hi <= start || lo >= end) {
-        uint32_t L = 0;
-        while ((1u << L) < hi - lo) L++;   // subtree [lo, hi) = node lo >> L of level L
-        out.emplace_back(L, lo >> L);
-        return;
-    }
-    if (hi - lo == 1) return;
-    uint32_t k = 1;
-    while (2 * k < hi - lo) k *= 2;   // largest power of two < n (RFC-6962 split)
-    prove_nodes(lo, lo + k, start, end, out);
-    prove_nodes(lo + k, hi, start, end, out);
-}
 
 }  // namespace
 

@@ -40,7 +40,7 @@
 #include "../../include/cda.h"
 #include "engine.h"
 #include "leaf_dev.h"
-#include "sha256_dev.h"
+#include "sha_bytes_dev.h"
 
 namespace cda {
 
@@ -73,112 +73,6 @@ struct VerifyBatch {
     uint8_t* verdict;            // per proof
 };
 
-// SHA-256 of tag || a[0:na] || b[0:nb] (byte addressed, any lengths),
-// big-endian state words.
-__device__ void sha_cat(uint32_t tag, const uint8_t* a, uint32_t na, const uint8_t* b, uint32_t nb,
-                        uint32_t (&out)[8]) {
-    ShaState st;
-    sha_init(st);
-    const uint32_t total = 1 + na + nb;
-    const uint32_t n_blocks = (total + 9 + 63) / 64;
-    auto byte_at = [&](uint32_t i) -> uint32_t {
-        if (i == 0) return tag;
-        if (i <= na) return a[i - 1];
-        if (i < total) return b[i - 1 - na];
-        if (i == total) return 0x80u;
-        return 0;
-    };
-#pragma unroll 1
-    for (uint32_t blk = 0; blk < n_blocks; blk++) {
-        uint32_t w[16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const uint32_t p = blk * 64 + 4 * j;
-            w[j] = (byte_at(p) << 24) | (byte_at(p + 1) << 16) | (byte_at(p + 2) << 8) | byte_at(p + 3);
-        }
-        if (blk == n_blocks - 1) {
-            w[14] = 0;
-            w[15] = total * 8;
-        }
-        sha_compress(st, w);
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++) out[j] = st.h[j];
-}
-
-__device__ __forceinline__ void store_digest_bytes(uint8_t* o, const uint32_t (&d)[8]) {
-    for (int j = 0; j < 8; j++) {
-        o[4 * j + 0] = (uint8_t)(d[j] >> 24);
-        o[4 * j + 1] = (uint8_t)(d[j] >> 16);
-        o[4 * j + 2] = (uint8_t)(d[j] >> 8);
-        o[4 * j + 3] = (uint8_t)d[j];
-    }
-}
-
-// Big-endian words of 32 bytes at a 4-byte aligned address.
-__device__ __forceinline__ void load_digest_be(const uint8_t* p, uint32_t (&d)[8]) {
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-#pragma unroll
-    for (int j = 0; j < 8; j++) d[j] = bswap32(q[j]);
-}
-
-// Big-endian slot words of a packed 90-B node at any byte address.
-__device__ __forceinline__ void load_packed_be(const uint8_t* p, uint32_t (&w)[kSlotWords]) {
-#pragma unroll
-    for (int t = 0; t < 22; t++)
-        w[t] = ((uint32_t)p[4 * t] << 24) | ((uint32_t)p[4 * t + 1] << 16) | ((uint32_t)p[4 * t + 2] << 8) | p[4 * t + 3];
-    w[22] = ((uint32_t)p[88] << 24) | ((uint32_t)p[89] << 16);
-    w[23] = 0;
-}
-
-// The 29-byte, 512-byte leaf digest sha256(0x00 || ns || share): leaf_dev.h's
-// streaming of the share (64-B chunks of raw words, one v_perm per message
-// word) with the namespace given by the proof instead of read from the share.
-// nsw: big-endian namespace words (byte 28 in the top byte of nsw[7]).
-__device__ __forceinline__ void leaf29_digest(const uint8_t* __restrict__ share, const uint32_t (&nsw)[8],
-                                              uint32_t (&d)[8]) {
-    const uint4* src = reinterpret_cast<const uint4*>(share);
-    ShaState st;
-    sha_init(st);
-    uint32_t cur[16], nxt[16], tail[8], w[16];
-    load_raw16(src, cur);
-    load_raw16(src + 4, nxt);
-    // block 0: 0x00 || ns(29) || share[0:34]
-    w[0] = nsw[0] >> 8;
-#pragma unroll
-    for (int i = 1; i < 7; i++) w[i] = funnel8(nsw[i - 1], nsw[i], 1);
-    w[7] = (nsw[6] << 24) | ((nsw[7] >> 24) << 16) | __builtin_amdgcn_perm(cur[0], cur[0], 0x0C0C0001u);
-#pragma unroll
-    for (int i = 8; i < 16; i++) w[i] = body_word(cur[i - 8], cur[i - 7]);
-    sha_compress(st, w);
-#pragma unroll
-    for (int i = 0; i < 8; i++) tail[i] = cur[8 + i];
-#pragma unroll 1
-    for (int b = 1; b < 8; b++) {
-#pragma unroll
-        for (int i = 0; i < 16; i++) cur[i] = nxt[i];
-        if (b < 7) load_raw16(src + 4 * (b + 1), nxt);
-#pragma unroll
-        for (int t = 0; t < 7; t++) w[t] = body_word(tail[t], tail[t + 1]);
-        w[7] = body_word(tail[7], cur[0]);
-#pragma unroll
-        for (int t = 8; t < 16; t++) w[t] = body_word(cur[t - 8], cur[t - 7]);
-#pragma unroll
-        for (int i = 0; i < 8; i++) tail[i] = cur[8 + i];
-        sha_compress(st, w);
-    }
-    // block 8: share words 120..127 then padding (542-B message)
-#pragma unroll
-    for (int t = 0; t < 7; t++) w[t] = body_word(tail[t], tail[t + 1]);
-    w[7] = __builtin_amdgcn_perm(tail[7], tail[7], 0x02030C0Cu) | 0x8000u;
-#pragma unroll
-    for (int t = 8; t < 15; t++) w[t] = 0;
-    w[15] = kLeafMsgBits;
-    sha_compress(st, w);
-#pragma unroll
-    for (int j = 0; j < 8; j++) d[j] = st.h[j];
-}
-
 // Leaf nodes of every share of the batch.  FAST: ns_len 29, share_len 512,
 // 96-B slots; otherwise byte nodes of node_len bytes at `stride`.
 template <bool FAST>
@@ -198,6 +92,8 @@ __global__ __launch_bounds__(256) void vp_leaf_kernel(const VerifyBatch b) {
     uint32_t d[8];
     if constexpr (FAST) {
         uint32_t nsw[8];
+        // load_ns_bytes(nid, false, nsw) (sha_bytes_dev.h), written out: through
+        // the call the first compression's constants are folded differently
 #pragma unroll
         for (int j = 0; j < 8; j++) {
             uint32_t v = 0;

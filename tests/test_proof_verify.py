@@ -337,6 +337,54 @@ def test_non_power_of_two_trees(ctx, cell_len, counts):
                 assert gpr.nmt_verify_inclusion(other, nodes, s, e, ns, cells[s:e], ctx) is False, (n, s, e)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("ns_len", [13, 14])
+def test_byte_node_padding_edges(ctx, ns_len):
+    """The byte-addressed path (any namespace length) at the SHA-256 padding
+    edges: 41-byte shares under a 13- / 14-byte namespace give leaf messages of
+    55 / 56 bytes (the 0x80 and bit count fit the block / spill into a second)
+    and node messages 0x01 || l || r of 117 / 121 bytes (two blocks / a
+    third).  Trees of 5 and 8 leaves built with the oracle's hashers, every
+    range: the verdicts of the oracle for the proof and for the proof with one
+    byte of one node flipped."""
+    nid = bytes(range(0x30, 0x30 + ns_len))
+    rnd = np.random.default_rng(ns_len)
+    shares = [rnd.integers(0, 256, 41, dtype=np.uint8).tobytes() for _ in range(8)]
+    leaf_nodes = [opr._nmt_leaf(ns_len, nid + s) for s in shares]
+    assert len(nid + shares[0]) + 1 == 42 + ns_len and 2 * len(leaf_nodes[0]) + 1 == (117, 121)[ns_len - 13]
+
+    for n in (5, 8):
+        def subtree(lo, hi):
+            if hi - lo == 1:
+                return leaf_nodes[lo]
+            k = opr.split_point(hi - lo)
+            return opr._nmt_node(ns_len, subtree(lo, lo + k), subtree(lo + k, hi))
+
+        def prove(lo, hi, s, e, out):
+            if hi <= s or lo >= e:
+                out.append(subtree(lo, hi))
+            elif hi - lo > 1:
+                k = opr.split_point(hi - lo)
+                prove(lo, lo + k, s, e, out)
+                prove(lo + k, hi, s, e, out)
+            return out
+
+        root = subtree(0, n)
+        for s in range(n):
+            for e in range(s + 1, n + 1):
+                nodes = prove(0, n, s, e, [])
+                want = opr.nmt_verify_inclusion(root, nodes, s, e, nid, shares[s:e])
+                assert want is True, (n, s, e)
+                assert gpr.nmt_verify_inclusion(root, nodes, s, e, nid, shares[s:e], ctx) is want, (n, s, e)
+                if not nodes:
+                    continue
+                q = (s + e) % len(nodes)
+                bad = nodes[:q] + [flip(nodes[q], (7 * s + 3 * e) % len(nodes[q]), e % 8)] + nodes[q + 1:]
+                want = opr.nmt_verify_inclusion(root, bad, s, e, nid, shares[s:e])
+                assert want is False, (n, s, e)
+                assert gpr.nmt_verify_inclusion(root, bad, s, e, nid, shares[s:e], ctx) is want, (n, s, e)
+
+
 def raw_call(ctx, b):
     verdict = np.full(4, 255, dtype=np.uint8)
     rc = ctx.lib.cda_share_proofs_verify(ctx.h, C.byref(b), _lib.ptr(verdict))

@@ -153,6 +153,12 @@ def test_prove_range_on_gpu(ctx, k):
     (8, 11, 512, [0, 8]),                # ragged leaf count
     (4, 8, 64, [1, 2]),                  # 64-B chunks (rsmt2d chunk size)
     (128, 256, 512, list(range(64, 192))),   # pkg/inclusion/nmt_caching.go: many rows at once
+    # padding edges of the byte-addressed SHA-256: leaf messages 0x00 || ns(29) || cell of
+    # 63, 64, 119 and 120 bytes (the 0x80 and the bit count spill into one more block from 56 / 120)
+    (4, 5, 33, [5, 1, 3]),
+    (4, 5, 34, [5, 1, 3]),
+    (4, 5, 89, [5, 1, 3]),
+    (4, 5, 90, [5, 1, 3]),
 ])
 def test_axis_roots_batch_on_gpu(ctx, k, n_cells, cell_len, axes):
     rng = np.random.default_rng(k * 1000 + n_cells)
@@ -162,6 +168,26 @@ def test_axis_roots_batch_on_gpu(ctx, k, n_cells, cell_len, axes):
     roots = wrapper.axis_roots(cells, k, axes, ctx)
     for t, ax in enumerate(axes):
         assert roots[t].tobytes() == pyref.axis_root(list(cells[t]), k, ax), (t, ax)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size", [0, 54, 55, 62, 63, 118, 119])
+def test_merkle_root_padding_edges_on_gpu(ctx, size):
+    """cda_merkle_root over items whose leaf message 0x00 || item is 1, 55, 56,
+    63, 64, 119 or 120 bytes: the last block holds the 0x80 and the bit count
+    up to 55 and 119 bytes, from 56 and 120 they spill into one more block.
+    1, 2, 3 and 5 items: a lone leaf, a pair, and the odd node promoted at the
+    first and at the second level."""
+    import ctypes as C
+    rng = np.random.default_rng(size)
+    for n in (1, 2, 3, 5):
+        items = [rng.integers(0, 256, size, dtype=np.uint8).tobytes() for _ in range(n)]
+        flat = np.frombuffer(b"".join(items) + b"\x00", dtype=np.uint8).copy()
+        off = (np.arange(n + 1, dtype=np.uint64) * size).astype(np.uint64)
+        out = np.empty(32, dtype=np.uint8)
+        ctx.check(ctx.lib.cda_merkle_root(ctx.h, wrapper.ptr(flat), off.ctypes.data_as(C.POINTER(C.c_uint64)), n,
+                                          wrapper.ptr(out)))
+        assert out.tobytes() == pyref.merkle_root(items), (size, n)
 
 
 @pytest.mark.gpu
