@@ -9,6 +9,7 @@
 //   5. RFC-6962 data root                           (DataAvailabilityHeader.Hash)
 #include "knobs.h"
 #include "engine.h"
+#include "hash_plan.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -252,33 +253,12 @@ Gf16Dev Engine::gf16(uint32_t k) const {
 
 static bool pow2(uint64_t x) { return x && !(x & (x - 1)); }
 
-// Nodes per tree at which the NMT levels switch from one wide launch per level
-// to tree_top_kernel (0 = never): the first level whose parents, over all 2W
-// trees of the n squares, fill less than one wave per SIMD of the chip
-// (1024 SIMDs x 64 lanes) -- lane pairs from there -- and then up to
-// top_wide_ (CDA_TOP_WIDE) levels more, while the lane pairs of the level
-// below the first fit in two waves per SIMD: the first of them runs a thread
-// per parent inside the tree top (*wide), which saves their per-level
-// launches (drain tail + boundary each).  CDA_TOP_FUSE=0 disables, =N forces
-// N (not wide).
+static_assert(kPlanSlot == (uint32_t)kSlot, "hash_plan.h plans scratch in node slots");
+
+// The fused tree top of a batch (hash_plan.h top_fuse_nodes) under this
+// context's CDA_TOP_FUSE / CDA_TOP_WIDE values.
 uint32_t Engine::top_fuse_nodes(uint32_t W, uint32_t n, bool* wide) const {
-    if (wide) *wide = false;
-    if (top_fuse_ >= 0) return (uint32_t)top_fuse_ <= W && top_fuse_ <= 256 ? (uint32_t)top_fuse_ : 0;
-    for (uint32_t m = W; m >= 2; m /= 2) {
-        if ((uint64_t)n * 2 * W * (m / 2) >= 65536) continue;
-        if (m > 256) return 0;
-        uint32_t t = m;
-        // the wide first level runs lane pairs above it: none without pairs
-        // (a one-thread-per-parent top holds at most 256 nodes)
-        const int widen = pair_sha_enabled() ? top_wide_ : 0;
-        for (int e = 0; e < widen && 2 * t <= W && 2 * t <= 512 && 2 * t >= 8 &&
-                        2 * (uint64_t)n * 2 * W * (t / 2) <= 131072;
-             e++)
-            t *= 2;
-        if (wide) *wide = t > m;
-        return t;
-    }
-    return 0;
+    return cda::top_fuse_nodes(W, n, top_fuse_, top_wide_, pair_sha_enabled(), wide);
 }
 
 int Engine::order_begin(hipStream_t s) {
@@ -411,31 +391,20 @@ int Engine::run_forests(Forest* f, uint32_t n_forest, uint32_t n_in, uint32_t n,
     // two streams (n <= 256) each launch holds only its part's lanes, so the
     // lane bound is per launch.
     uint32_t m0 = n_in;
-    if (subtrees && subtree_min_ > 0 && stop >= 1 && n_in % stop == 0) {
-        uint64_t per_node = 0;   // lanes per subtree root per tree
-        for (uint32_t i = 0; i < n_forest; i++) per_node += (uint64_t)n * f[i].n_trees;
-        uint32_t sub = stop;
+    if (subtrees && n_forest <= 2) {
         // default target: 524288 lanes (8 waves per SIMD, 2.67 rounds at the
         // kernel's 3 waves per SIMD, the shape of config 4's whole-tree launch)
         // for trees of <= 512 leaves -- config 4's per-GPU shards of 64 / 128
         // / 256 squares +4-5 % over 131072 lanes on two streams (round 5,
         // profiles/r05/subtree_lanes_ab.txt); 262144 for trees of >= 1024
         // leaves (k >= 512: one k = 512 square 1.096 -> 1.087 ms, 8- instead
-        // of 16-leaf subtrees; profiles/r03at/).  Subtrees keep >= 8 leaves
-        // (CDA_SUBTREE); a batch too small to reach the target still takes the
-        // fused launch when it holds 131072 lanes.
-        const uint64_t want = subtree_lanes_ ? subtree_lanes_ : n_in >= 1024 ? 262144u : 524288u;
-        // launch_subtrees needs subtrees of >= 4 leaves: a smaller CDA_SUBTREE
-        // setting means per-level launches, not a failing launch
-        const uint32_t min_leaves = (uint32_t)std::max(subtree_min_, 4);
-        while (sub < n_in && 2 * (uint64_t)sub * min_leaves <= n_in && per_node * sub < want) sub *= 2;
-        bool fits = per_node * sub >= std::min<uint64_t>(want, 131072) && sub < n_in && n_in / sub >= min_leaves;
-        const uint32_t slog = fits ? (uint32_t)__builtin_ctz(n_in / sub) : 0;
-        for (uint32_t i = 0; i < n_forest && fits; i++) {
-            const uint64_t need = (uint64_t)f[i].n_trees * sub * slog * kSlot;
-            const uint64_t room = n_forest > 1 ? out_off[1] - out_off[0] : buf_sq;
-            fits = need <= room && f[i].n_trees % 64 == 0;
-        }
+        // of 16-leaf subtrees; profiles/r03at/).  The choice itself:
+        // hash_plan.h subtree_sub.
+        uint32_t n_trees[2] = {0, 0};
+        for (uint32_t i = 0; i < n_forest && i < 2; i++) n_trees[i] = f[i].n_trees;
+        const uint64_t room = n_forest > 1 ? out_off[1] - out_off[0] : buf_sq;
+        const uint32_t sub = subtree_sub(n_in, stop, n, n_trees, n_forest, room, subtree_min_, subtree_lanes_);
+        const bool fits = sub != 0;
         if (fits) {
             for (uint32_t i = 0; i < n_forest; i++) {
                 f[i].out = out + out_off[i];
@@ -562,13 +531,10 @@ int Engine::dah_finish(uint32_t k, uint32_t i0, uint32_t n, uint32_t from, const
     // parents; the latency-bound rest of the trees (and the data root's RFC
     // leaf digests) in one tree_top_kernel launch.
     // (from == 1: the chunks already produced the roots -- no tree top)
-    bool wide = false;
-    uint32_t top = from > 1 ? top_fuse_nodes(W, n, &wide) : 0;
+    const TopChoice tc = finish_top(W, n, from, top_fuse_, top_wide_, pair_sha_enabled());
+    const uint32_t top = tc.top;
+    const bool wide = tc.wide;
     uint32_t n_dig = 2 * W;   // digests per square the tree top leaves for the data root
-    if (top > from) {
-        top = from;
-        wide = false;
-    }
     if (from > 1) {
         const uint32_t stop = top ? top : 1;
         mark_begin(kStageLevels, s);
@@ -631,9 +597,8 @@ int Engine::enqueue_dah(const uint8_t* d_eds, uint32_t k, uint32_t n, uint8_t* d
     // 64 / 128 / 256 squares ran 4-5 % faster on one stream
     // (profiles/r05/subtree_lanes_ab.txt); two parts stay for small batches,
     // whose latency-bound tails the second stream overlaps.
-    const uint32_t want = hash_split_ >= 0 ? (uint32_t)hash_split_ : (n < 64 && k <= 128 ? 2u : 1u);
-    const uint32_t parts = std::min<uint32_t>(std::min<uint32_t>(want, n), kMaxHashParts);
-    if (parts > 1 && !profiling_) {
+    const uint32_t parts = hash_parts(k, n, hash_split_, profiling_);
+    if (parts > 1) {
         hipEvent_t go = sync_event(0);
         if (!go || !sync_event(parts)) return fail(CDA_ERR_DEVICE, "hipEventCreate failed");
         if ((rc = check(hipEventRecord(go, s), "hipEventRecord"))) return rc;
@@ -648,7 +613,7 @@ int Engine::enqueue_dah(const uint8_t* d_eds, uint32_t k, uint32_t n, uint8_t* d
         int err = CDA_OK;
         uint32_t joined_from = parts;   // side parts [joined_from, parts) recorded their end on sync_event(p)
         for (uint32_t p = parts; p-- > 0;) {
-            const uint32_t i0 = p * n / parts, i1 = (p + 1) * n / parts;
+            const uint32_t i0 = hash_part_begin(p, n, parts), i1 = hash_part_begin(p + 1, n, parts);
             hipStream_t q = s;
             if (p) {
                 if ((rc = split_stream(p - 1, &q))) {

@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "cda_kernels.h"
+#include "hash_plan.h"
 #include "sha256_dev.h"
 #include "leaf_dev.h"
 
@@ -397,9 +398,8 @@ __device__ __forceinline__ void data_root_level(const uint32_t* __restrict__ in,
 // lanes: a k = 512 square's first level; data root 0.055 -> 0.049 ms,
 // profiles/r05/data_root_pairs_ab.txt -- at config 4's 1 024 squares the
 // 512-thread launch made the stage 0.143 -> 0.209 ms, so not there).
-constexpr uint32_t kPairMaxParents = 128;
-constexpr uint32_t kPairMaxParentsSmall = 256;
-constexpr uint32_t kPairSmallSquares = 8;   // launches of <= this many squares
+// (kPairMaxParents = 128, kPairMaxParentsSmall = 256, kPairSmallSquares = 8:
+// hash_plan.h, with the launch arithmetic that uses them)
 
 // 16 rounds [R0, R0 + 16) of a lane-pair compression over precomputed
 // K + W words (v: the pair's 4 state words, as in sha_pair_compress).
@@ -584,7 +584,7 @@ __device__ __forceinline__ void data_root_levels(const uint32_t* D, uint32_t n, 
 // spread over all workgroups instead of one per square.  PAIR: a lane pair
 // per parent (kTopThreads pairs).
 // ---------------------------------------------------------------------------
-constexpr uint32_t kTopThreads = 128;   // parents per workgroup: tpw = 256 / n_in trees x n_in / 2
+// kTopThreads = 128 (hash_plan.h): parents per workgroup, tpw = 256 / n_in trees x n_in / 2
 
 // flags: kTopHelpers -- schedule-helper waves in the narrow levels (PAIR);
 // kTopWide -- the first level runs a thread per parent over 2 kTopThreads
@@ -905,7 +905,7 @@ static uint32_t hash_grid(uint32_t nblocks) {
         const int per = e ? atoi(e) : 0;
         return per > 0 ? (uint32_t)per * device_cus() : 0u;
     }();
-    return cap && nblocks > cap ? cap : nblocks;
+    return hash_grid_for(nblocks, cap);
 }
 
 // CDA_LEAF_PAIR_MAX: cells per launch up to which the lane-pair leaf kernel
@@ -921,7 +921,7 @@ static uint64_t leaf_pair_max() {
 hipError_t launch_leaves(const CellGrid& g, uint32_t n, uint8_t* slots, uint32_t* err, bool check_rows,
                          bool check_cols, hipStream_t s) {
     const uint64_t cells = (uint64_t)g.rows * g.cols * n;
-    if (cells > 0 && cells <= leaf_pair_max() && pair_sha_enabled()) {
+    if (leaves_pair(cells, leaf_pair_max(), pair_sha_enabled())) {
         const uint32_t nbx2 = (g.rows * g.cols + 127) / 128;
         hipLaunchKernelGGL(leaf_pair_kernel, dim3(nbx2 * n), dim3(256), 0, s, g, slots, err, check_rows ? 1 : 0,
                            check_cols ? 1 : 0, nbx2);
@@ -984,40 +984,31 @@ static uint32_t data_root_mode() {
         const char* e = test_knob("CDA_DR_HELPERS");
         return !(e && atoi(e) == 0);
     }();
-    return pair_sha_enabled() ? (dr_helpers ? 2u : 1u) : 0u;
+    return data_root_mode_for(pair_sha_enabled(), dr_helpers);
 }
 
 hipError_t launch_tree_top(const Forest* f, uint32_t n_forest, uint32_t n_in, uint32_t n, uint32_t* dig,
                            uint32_t n_items, hipStream_t s, uint32_t* n_dig_out, bool wide) {
-    wide = wide && pair_sha_enabled();
-    if (n_forest < 1 || n_forest > 2 || n_in < (wide ? 8u : 2u) || n_in > (wide ? 4 : 2) * kTopThreads ||
-        (n_in & (n_in - 1)))
-        return hipErrorInvalidValue;
+    if (n_forest < 1 || n_forest > 2) return hipErrorInvalidValue;
     Forest2 fs{};
     uint32_t trees = 0;
     for (uint32_t i = 0; i < n_forest; i++) {
         fs.f[i] = f[i];
         trees += f[i].n_trees;
     }
-    const uint32_t tpw = (wide ? 4 : 2) * kTopThreads / n_in;   // trees per workgroup
-    // RFC-6962 levels inside the workgroups: while every workgroup holds tpw
-    // of the n_items (a power of two) roots and at least 2 digests per square
-    // remain for data_root_digest_kernel
-    uint32_t lv = 0;
-    if (dig && trees == n_items && (n_items & (n_items - 1)) == 0 && tpw <= n_items)
-        while ((2u << lv) <= tpw && (n_items >> (lv + 1)) >= 2) lv++;
     static const bool rfc_in_top = [] {   // CDA_TOP_RFC=0: leaf digests only (A/B knob)
         const char* e = test_knob("CDA_TOP_RFC");
         return !(e && atoi(e) == 0);
     }();
-    if (!rfc_in_top) lv = 0;
-    const uint32_t n_dig = n_items >> lv;
+    // trees per workgroup, the RFC-6962 levels inside the workgroups, lane
+    // pairs or a thread per parent: hash_plan.h tree_top_launch
+    const TopLaunch t = tree_top_launch(n_in, n, trees, n_items, dig != nullptr, wide, pair_sha_enabled(), rfc_in_top);
+    if (!t.valid) return hipErrorInvalidValue;
+    wide = t.wide;
+    const uint32_t tpw = t.tpw, lv = t.lv, n_dig = t.n_dig;
     if (n_dig_out) *n_dig_out = n_dig;
-    // lane pairs while they still fit in a wave per SIMD (1024 SIMDs); wide:
-    // the caller's choice (a thread per parent in the first level)
-    const uint64_t parents = (uint64_t)n * trees * (n_in / 2);
-    const bool pair = wide || (pair_sha_enabled() && 2 * parents <= 65536);
-    const dim3 grid((trees + tpw - 1) / tpw, n);
+    const bool pair = t.pair;
+    const dim3 grid(t.grid_x, n);
     // CDA_TOP_HELPERS=0 (A/B knob): no schedule-helper waves in the narrow levels
     static const uint32_t helpers = [] {
         const char* e = test_knob("CDA_TOP_HELPERS");
@@ -1070,14 +1061,11 @@ hipError_t launch_data_root_digests(const uint32_t* dig, uint32_t n_items, uint3
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    // a thread per first-level parent (<= 512: more would cap the kernel at
-    // 128 VGPRs and spill the helpers' registers), and room for the lane pairs
-    const uint32_t pmax = n <= kPairSmallSquares ? kPairMaxParentsSmall : kPairMaxParents;
-    uint32_t threads = std::min<uint32_t>(n_items / 2, 512);
-    threads = std::max<uint32_t>(threads, std::min<uint32_t>(n_items, 2 * pmax));
-    threads = std::max<uint32_t>((threads + 63) / 64 * 64, 64);
+    // threads and the largest pair level: hash_plan.h data_root_launch
+    const DataRootLaunch d = data_root_launch(n_items, n, data_root_mode());
+    const uint32_t threads = d.threads;
     // mode in the low byte, the largest pair level above it
-    const uint32_t mode = data_root_mode() | pmax << 8;
+    const uint32_t mode = d.mode | d.pmax << 8;
     hipLaunchKernelGGL(data_root_digest_kernel, dim3(n), dim3(threads), lds, s, dig, n_items, data_roots,
                        status ? err : nullptr, status, mode);
     return hipGetLastError();

@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "cda_kernels.h"
+#include "hash_plan.h"
 #include "leopard_tables.h"
 
 namespace cda {
@@ -196,7 +197,7 @@ hipError_t launch_rs8_job(const RsJob& j, uint32_t k, uint32_t n, hipStream_t s)
     // multiple of its 4-codeword workgroup (or CDA_RS8_BYTEFORM=1 forces this
     // byte-form encoder, for A/B measurement).
     static const bool byteform = test_knob("CDA_RS8_BYTEFORM") && atoi(test_knob("CDA_RS8_BYTEFORM"));
-    if (k == 128 && !byteform && j.seg[0].n_cw % 4 == 0 && (j.n_seg < 2 || j.seg[1].n_cw % 4 == 0))
+    if (rs8_bitsliced(k, byteform, j.seg[0].n_cw, j.n_seg < 2 ? 0 : j.seg[1].n_cw))
         return launch_rs8_bs(j, n, s);
     switch (k) {
         case 1: return launch_job<1>(j, n, s);

@@ -23,6 +23,7 @@
 #include "knobs.h"
 #include "bitslice8.h"
 #include "cda_kernels.h"
+#include "hash_plan.h"
 
 namespace cda {
 
@@ -369,7 +370,7 @@ hipError_t launch_rs8_bs(const RsJob& j, uint32_t n, hipStream_t s) {
             const char* e = test_knob("CDA_RS8_ONE");
             return e ? atoi(e) : -1;
         }();
-        const bool one = one_env >= 0 ? one_env != 0 : (uint64_t)ncw * n < 2u * 256u;
+        const bool one = rs8_one_per_wg(ncw, n, one_env);
         // batches: XCD-aware 128-B slices (CDA_RS8_SLICE=0 turns them off, A/B knob)
         static const int slice_env = [] {
             const char* e = test_knob("CDA_RS8_SLICE");

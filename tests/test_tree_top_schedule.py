@@ -2,11 +2,13 @@
 the wide first level (kTopWide: a thread per parent over 2 kTopThreads
 parents, tpw = 4 kTopThreads / n_in trees per workgroup, its output in the
 helpers' LDS rows, lane pairs from the second level on), and of the engine's
-choice of the fused top (engine.hip top_fuse_nodes).  Nodes are combined with
+choice of the fused top (hash_plan.h top_fuse_nodes).  Nodes are combined with
 an order-sensitive stand-in for hash_node, so a wrong pairing, tree offset or
 buffer alias changes the roots.  The GPU parity tests check the kernel itself
 (k = 128 / 256 / 512 squares against the oracle fixtures)."""
 import pytest
+
+import hash_plan_tool
 
 K_TOP_THREADS = 128
 
@@ -75,7 +77,7 @@ def test_tree_top_indexing(n_in, wide, n_trees):
 
 
 def top_fuse_nodes(W, n, top_wide=2):
-    """engine.hip Engine::top_fuse_nodes (auto mode): (top, wide)."""
+    """hash_plan.h top_fuse_nodes (auto mode): (top, wide)."""
     m = W
     while m >= 2:
         if n * 2 * W * (m // 2) < 65536:
@@ -109,3 +111,19 @@ def test_top_fuse_choice():
             if wide:
                 # the lane pairs of the second level fit two waves per SIMD
                 assert 8 <= t and 2 * n * 2 * W * (t // 4) <= 131072
+
+
+@pytest.mark.skipif(not hash_plan_tool.HAVE_GXX, reason="g++ not available")
+def test_top_fuse_mirror_equals_hash_plan_header():
+    """The Python mirror above against csrc/hash_plan.h itself (printed by
+    tools/hash_plan_host_test.cpp): every W and n test_top_fuse_choice loops
+    over or names, with CDA_TOP_WIDE's default 2 and 0."""
+    table = hash_plan_tool.top_fuse_table()
+    cases = {(W, n) for W in (4, 8, 16, 32, 64, 128, 256, 512, 1024, 2048) for n in (1, 2, 3, 4, 8, 16, 64, 256)}
+    cases |= {(256, 1), (1024, 1), (512, 1), (256, 128), (4, 1)}
+    for W, n in sorted(cases):
+        for top_wide in (0, 2):
+            assert top_fuse_nodes(W, n, top_wide=top_wide) == table[(W, n, top_wide)], (W, n, top_wide)
+    # and over the tool's whole range
+    for (W, n, top_wide), want in table.items():
+        assert top_fuse_nodes(W, n, top_wide=top_wide) == want, (W, n, top_wide)
