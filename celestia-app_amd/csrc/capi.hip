@@ -141,6 +141,33 @@ int plan_square(const uint8_t* txs, const uint64_t* tx_off, uint32_t n_txs, uint
                              mode == CDA_SQUARE_BUILD ? cda::square::kBuild : cda::square::kConstruct, p, err);
 }
 
+// The plan's kept transaction indexes into the caller's optional outputs.
+void copy_kept(const cda::square::Plan& p, uint32_t* kept, uint32_t* n_kept) {
+    if (!kept) return;
+    memcpy(kept, p.kept.data(), p.kept.size() * 4);
+    if (n_kept) *n_kept = (uint32_t)p.kept.size();
+}
+
+// A host-only entry point (no device work), usable without a context:
+// run(&err) returns a CDA_* code and the error text.
+template <class F>
+int host_only(cda_ctx* ctx, F&& run) {
+    if (!ctx) {
+        tl_err.msg.clear();
+        try {
+            return run(&tl_err.msg);
+        } catch (const std::bad_alloc&) {
+            tl_err.msg = "host allocation failed";
+            return CDA_ERR_OOM;
+        }
+    }
+    return guarded(ctx, [&](cda::Engine& e) -> int {
+        std::string err;
+        const int rc = run(&err);
+        return rc ? e.fail(rc, err) : CDA_OK;
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -274,10 +301,7 @@ int cda_data_root(cda_ctx* ctx, const uint8_t* row_roots, const uint8_t* col_roo
     return guarded(ctx, [&](cda::Engine& e) -> int {
         if (!data_root) return e.fail(CDA_ERR_INVALID, "null buffer");
         if (w == 0) {  // merkle.HashFromByteSlices(nil) = sha256("")
-            static const uint8_t empty[32] = {0xe3, 0xb0, 0xc4, 0x42, 0x98, 0xfc, 0x1c, 0x14, 0x9a, 0xfb, 0xf4,
-                                              0xc8, 0x99, 0x6f, 0xb9, 0x24, 0x27, 0xae, 0x41, 0xe4, 0x64, 0x9b,
-                                              0x93, 0x4c, 0xa4, 0x95, 0x99, 0x1b, 0x78, 0x52, 0xb8, 0x55};
-            memcpy(data_root, empty, 32);
+            memcpy(data_root, cda::kSha256Empty, 32);
             return CDA_OK;
         }
         if (w & (w - 1)) return e.fail(CDA_ERR_UNSUPPORTED, "root count must be a power of two");
@@ -357,20 +381,7 @@ int cda_square_tx_share_range(cda_ctx* ctx, const uint8_t* txs, const uint64_t* 
         if (is_pfb) *is_pfb = tx_index >= p.n_normal;
         return CDA_OK;
     };
-    if (!ctx) {
-        tl_err.msg.clear();
-        try {
-            return run(&tl_err.msg);
-        } catch (const std::bad_alloc&) {
-            tl_err.msg = "host allocation failed";
-            return CDA_ERR_OOM;
-        }
-    }
-    return guarded(ctx, [&](cda::Engine& e) -> int {
-        std::string err;
-        const int rc = run(&err);
-        return rc ? e.fail(rc, err) : CDA_OK;
-    });
+    return host_only(ctx, run);
 }
 
 int cda_square_layout(cda_ctx* ctx, const uint8_t* txs, const uint64_t* tx_off, uint32_t n_txs,
@@ -385,10 +396,7 @@ int cda_square_layout(cda_ctx* ctx, const uint8_t* txs, const uint64_t* tx_off, 
         cda::square::Plan p;
         if (plan_square(txs, tx_off, n_txs, max_square_size, threshold, mode, &p, err)) return CDA_ERR_SQUARE;
         *square_size = p.square_size;
-        if (kept) {
-            memcpy(kept, p.kept.data(), p.kept.size() * 4);
-            if (n_kept) *n_kept = (uint32_t)p.kept.size();
-        }
+        copy_kept(p, kept, n_kept);
         if (n_share_indexes) *n_share_indexes = (uint32_t)p.share_indexes.size();
         if (share_indexes) {
             if (p.share_indexes.size() > share_index_cap) {
@@ -399,20 +407,7 @@ int cda_square_layout(cda_ctx* ctx, const uint8_t* txs, const uint64_t* tx_off, 
         }
         return CDA_OK;
     };
-    if (!ctx) {
-        tl_err.msg.clear();
-        try {
-            return run(&tl_err.msg);
-        } catch (const std::bad_alloc&) {
-            tl_err.msg = "host allocation failed";
-            return CDA_ERR_OOM;
-        }
-    }
-    return guarded(ctx, [&](cda::Engine& e) -> int {
-        std::string err;
-        const int rc = run(&err);
-        return rc ? e.fail(rc, err) : CDA_OK;
-    });
+    return host_only(ctx, run);
 }
 
 int cda_square_construct(cda_ctx* ctx, const uint8_t* txs, const uint64_t* tx_off, uint32_t n_txs,
@@ -425,10 +420,7 @@ int cda_square_construct(cda_ctx* ctx, const uint8_t* txs, const uint64_t* tx_of
         if (plan_square(txs, tx_off, n_txs, max_square_size, threshold, mode, &p, &err))
             return e.fail(CDA_ERR_SQUARE, err);
         *square_size = p.square_size;
-        if (kept) {
-            memcpy(kept, p.kept.data(), p.kept.size() * 4);
-            if (n_kept) *n_kept = (uint32_t)p.kept.size();
-        }
+        copy_kept(p, kept, n_kept);
         if ((size_t)p.square_size * p.square_size * CDA_SHARE_SIZE > ods_capacity)
             return e.fail(CDA_ERR_INVALID, "ods capacity too small for the square");
         return e.host_square(p, txs, n_txs ? tx_off[n_txs] : 0, ods);
@@ -447,10 +439,7 @@ int cda_construct_extend_dah(cda_ctx* ctx, const uint8_t* txs, const uint64_t* t
         if (plan_square(txs, tx_off, n_txs, max_square_size, threshold, mode, &p, &err))
             return e.fail(CDA_ERR_SQUARE, err);
         *square_size = p.square_size;
-        if (kept) {
-            memcpy(kept, p.kept.data(), p.kept.size() * 4);
-            if (n_kept) *n_kept = (uint32_t)p.kept.size();
-        }
+        copy_kept(p, kept, n_kept);
         const size_t w = 2 * (size_t)p.square_size;
         if (w * CDA_NMT_ROOT_SIZE > roots_capacity) return e.fail(CDA_ERR_INVALID, "roots capacity too small");
         if (eds && w * w * CDA_SHARE_SIZE > eds_capacity) return e.fail(CDA_ERR_INVALID, "eds capacity too small");
@@ -470,10 +459,7 @@ int cda_square_construct_device(cda_ctx* ctx, const uint8_t* txs, const uint64_t
         if (plan_square(txs, tx_off, n_txs, max_square_size, threshold, mode, &p, &err))
             return e.fail(CDA_ERR_SQUARE, err);
         *square_size = p.square_size;
-        if (kept) {
-            memcpy(kept, p.kept.data(), p.kept.size() * 4);
-            if (n_kept) *n_kept = (uint32_t)p.kept.size();
-        }
+        copy_kept(p, kept, n_kept);
         if ((size_t)p.square_size * p.square_size * CDA_SHARE_SIZE > ods_capacity)
             return e.fail(CDA_ERR_INVALID, "ods capacity too small for the square");
         return e.enqueue_square(p, static_cast<const uint8_t*>(d_txs), static_cast<uint8_t*>(d_ods), s);
@@ -545,11 +531,10 @@ int cda_square_dah(cda_square* sq, uint32_t* k, uint8_t* row_roots, uint8_t* col
     if (!sq) return CDA_ERR_INVALID;
     return guarded(sq->ctx, [&](cda::Engine& e) -> int {
         if (k) *k = sq->sq.k;
-        int rc;
-        if (row_roots && (rc = e.square_read(&sq->sq, cda::ResidentSquare::kRowRoots, row_roots))) return rc;
-        if (col_roots && (rc = e.square_read(&sq->sq, cda::ResidentSquare::kColRoots, col_roots))) return rc;
-        if (data_root && (rc = e.square_read(&sq->sq, cda::ResidentSquare::kDataRoot, data_root))) return rc;
-        if (eds && (rc = e.square_read(&sq->sq, cda::ResidentSquare::kEds, eds))) return rc;
+        if (row_roots) CDA_TRY(e.square_read(&sq->sq, cda::ResidentSquare::kRowRoots, row_roots));
+        if (col_roots) CDA_TRY(e.square_read(&sq->sq, cda::ResidentSquare::kColRoots, col_roots));
+        if (data_root) CDA_TRY(e.square_read(&sq->sq, cda::ResidentSquare::kDataRoot, data_root));
+        if (eds) CDA_TRY(e.square_read(&sq->sq, cda::ResidentSquare::kEds, eds));
         return CDA_OK;
     });
 }
@@ -676,10 +661,7 @@ int cda_merkle_root(cda_ctx* ctx, const uint8_t* items, const uint64_t* off, uin
     return guarded(ctx, [&](cda::Engine& e) -> int {
         if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
         if (n == 0) {   // merkle.HashFromByteSlices(nil) = sha256("")
-            static const uint8_t empty[32] = {0xe3, 0xb0, 0xc4, 0x42, 0x98, 0xfc, 0x1c, 0x14, 0x9a, 0xfb, 0xf4,
-                                              0xc8, 0x99, 0x6f, 0xb9, 0x24, 0x27, 0xae, 0x41, 0xe4, 0x64, 0x9b,
-                                              0x93, 0x4c, 0xa4, 0x95, 0x99, 0x1b, 0x78, 0x52, 0xb8, 0x55};
-            memcpy(out, empty, 32);
+            memcpy(out, cda::kSha256Empty, 32);
             return CDA_OK;
         }
         if (!off || (off[n] > off[0] && !items)) return e.fail(CDA_ERR_INVALID, "null buffer");

@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "push_order.h"
+
 namespace cda {
 
 constexpr uint32_t kNoCopy = 0xFFFFFFFFu;
@@ -80,7 +82,7 @@ struct CellGrid {
 // NMT leaf hashing: one 96-B leaf slot per grid cell, slots[y][r][c].  Also
 // checks nmt push order inside Q0: along rows if check_rows (both cells in the
 // grid) and along columns if check_cols.  err[y] = min over violations of
-// (axis << 24 | axis_index << 12 | push_position) in global coordinates.
+// the push-order word (push_order.h) in global coordinates.
 hipError_t launch_leaves(const CellGrid& g, uint32_t n_squares, uint8_t* slots, uint32_t* err, bool check_rows,
                          bool check_cols, hipStream_t stream);
 // Push-order check of Q0 rows only, for a block of ODS rows held in
@@ -105,6 +107,14 @@ struct Forest {
     uint8_t* root_slots;
     uint64_t rslot_sq;
     uint32_t root0;
+    // the same forest with square i0 of the batch as its square 0 (host side)
+    Forest from_square(uint64_t i0) const {
+        Forest f = *this;
+        f.in += i0 * in_sq;
+        if (roots) f.roots += i0 * roots_sq;
+        if (root_slots) f.root_slots += i0 * rslot_sq;
+        return f;
+    }
 };
 // One level of up to two forests with the same n_in (blockIdx.z selects).
 hipError_t launch_level(const Forest* f, uint32_t n_forest, uint32_t n_in, uint32_t n_squares, hipStream_t stream);

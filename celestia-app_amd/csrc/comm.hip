@@ -62,10 +62,9 @@ int Engine::enqueue_split_rows_send(const uint8_t* d_rows, uint32_t k, uint32_t 
     const uint32_t W = 2 * k;
     if (parts == 0 || (parts & (parts - 1)) || parts > W || n_rows == 0)
         return fail(CDA_ERR_INVALID, "bad split: parts must be a power of two <= 2k");
-    int rc;
     if (parts == 1) return enqueue_split_rows(d_rows, k, n_rows, row0, d_send, d_err, s);   // [1][R][W] = [R][W]
-    if ((rc = check(split_blk_.ensure((size_t)n_rows * W * kShare), "hipMalloc row block"))) return rc;
-    if ((rc = enqueue_split_rows(d_rows, k, n_rows, row0, split_blk_.as<uint8_t>(), d_err, s))) return rc;
+    CDA_TRY(ensure(split_blk_, (size_t)n_rows * W * kShare, "hipMalloc row block"));
+    CDA_TRY(enqueue_split_rows(d_rows, k, n_rows, row0, split_blk_.as<uint8_t>(), d_err, s));
     // the layout of a split into `parts` column groups, with this call's row
     // count (cda_split_rows_send callers may pass any R)
     SplitLayout L(k, parts);
@@ -73,7 +72,7 @@ int Engine::enqueue_split_rows_send(const uint8_t* d_rows, uint32_t k, uint32_t 
     const uint64_t n16 = (uint64_t)n_rows * W * (kShare / 16);
     hipLaunchKernelGGL(group_rows_kernel, dim3((uint32_t)((n16 + 255) / 256)), dim3(256), 0, s,
                        split_blk_.as<uint4>(), d_send, L);
-    return check(hipGetLastError(), "group rows");
+    return launched("group rows");
 }
 
 int comm_unique_id(uint8_t* id) {
@@ -88,11 +87,10 @@ int Engine::comm_init(int rank, int world, const uint8_t* id) {
     comm_destroy();
     // the agreement round's words (split_extend_dah): preset 0 and 1, so the
     // all-reduce needs no copy that could fail before it
-    int rc;
-    if ((rc = check(comm_flag_.ensure_fixed(16), "hipMalloc agreement words"))) return rc;
+    CDA_TRY(check(comm_flag_.ensure_fixed(16), "hipMalloc agreement words"));
     const int32_t preset[4] = {0, 1, 0, 0};
-    if ((rc = check(hipMemcpy(comm_flag_.ptr, preset, sizeof preset, hipMemcpyHostToDevice), "hipMemcpy agreement words")))
-        return rc;
+    CDA_TRY(check(hipMemcpy(comm_flag_.ptr, preset, sizeof preset, hipMemcpyHostToDevice),
+            "hipMemcpy agreement words"));
     ncclUniqueId uid;
     memcpy(&uid, id, sizeof uid);
     ncclComm_t c = nullptr;
@@ -217,7 +215,6 @@ int Engine::split_extend_dah(const uint8_t* d_rows, uint32_t k, uint8_t* d_col_b
     if (!L.valid()) return fail(CDA_ERR_INVALID, "world size must divide k (a power of two <= 1024)");
     const uint32_t R = L.R, C = L.C;
     const size_t piece = L.piece();   // one rank pair's all-to-all block
-    int rc;
     // -- scratch + agreement (only when k changes; k is the same on every rank) --
     if (comm_k_ != k) {
         int ok = 1;
@@ -231,19 +228,18 @@ int Engine::split_extend_dah(const uint8_t* d_rows, uint32_t k, uint8_t* d_col_b
         if (ok && lvl_.ensure((size_t)W * C * kSlot) != hipSuccess) ok = 0;
         (void)hipGetLastError();
         int32_t* words = comm_flag_.as<int32_t>();
-        if ((rc = comm_group("ncclAllReduce (allocation agreement)", [&](void* c) {
+        CDA_TRY(comm_group("ncclAllReduce (allocation agreement)", [&](void* c) {
                  return (int)ncclAllReduce(words + (ok ? 1 : 0), words + 2, 1, ncclInt32, ncclMin,
                                            static_cast<ncclComm_t>(c), s);
-             })))
-            return rc;
+             }));
         int32_t h_ok = 0;
-        if ((rc = check(hipMemcpyAsync(&h_ok, words + 2, 4, hipMemcpyDeviceToHost, s), "D2H agreement word"))) return rc;
+        CDA_TRY(d2h(&h_ok, words + 2, 4, s, "D2H agreement word"));
         if (comm_fault("stall")) {   // tests: wait here as if a peer never arrived, until aborted
             for (int i = 0; i < 30000 && comm_alive(); i++) std::this_thread::sleep_for(std::chrono::milliseconds(1));
         }
         const hipError_t se = hipStreamSynchronize(s);
         if (!comm_alive()) return aborted(*this, "allocation agreement");
-        if ((rc = check(se, "hipStreamSynchronize"))) return rc;
+        CDA_TRY(check(se, "hipStreamSynchronize"));
         if (!h_ok)
             return fail(CDA_ERR_OOM, ok ? "a peer rank could not allocate its split scratch"
                                         : "split scratch allocation failed on this rank");
@@ -291,7 +287,7 @@ int Engine::split_extend_dah(const uint8_t* d_rows, uint32_t k, uint8_t* d_col_b
             return comm_fail("poison", ncclUnhandledCudaError);
         // 2. all-to-all: piece h goes to rank h; rank g's piece lands at rows
         //    g*R..g*R+R-1 of the column block
-        if ((rc = comm_group("all-to-all", [&](void* cv) -> int {
+        CDA_TRY(comm_group("all-to-all", [&](void* cv) -> int {
                  if (comm_fault("a2a")) return (int)ncclInternalError;
                  ncclComm_t comm = static_cast<ncclComm_t>(cv);
                  for (uint32_t h = 0; h < G; h++) {
@@ -302,8 +298,7 @@ int Engine::split_extend_dah(const uint8_t* d_rows, uint32_t k, uint8_t* d_col_b
                          return (int)q;
                  }
                  return (int)ncclSuccess;
-             })))
-            return rc;
+             }));
     }
     // 3. columns: Q2|Q3 parity, leaves, column roots, row subtrees
     if (!step([&] {
@@ -314,7 +309,7 @@ int Engine::split_extend_dah(const uint8_t* d_rows, uint32_t k, uint8_t* d_col_b
     if (comm_fault("peer") && hipMemsetAsync(err, 0x00, 4, s) != hipSuccess)   // tests: as if a peer had failed
         return comm_fail("poison", ncclUnhandledCudaError);
     // 4. gather the slots on rank 0 and reduce the push-order word
-    if ((rc = comm_group("gather", [&](void* cv) -> int {
+    CDA_TRY(comm_group("gather", [&](void* cv) -> int {
              if (comm_fault("gather")) return (int)ncclInternalError;
              ncclComm_t comm = static_cast<ncclComm_t>(cv);
              ncclResult_t q;
@@ -330,22 +325,20 @@ int Engine::split_extend_dah(const uint8_t* d_rows, uint32_t k, uint8_t* d_col_b
              }
              if ((q = ncclSend(row_sub, (size_t)W * kSlot, ncclUint8, 0, comm, s)) != ncclSuccess) return (int)q;
              return (int)ncclSend(col_slots, (size_t)C * kSlot, ncclUint8, 0, comm, s);
-         })))
-        return rc;
-    if ((rc = comm_group("ncclReduce", [&](void* cv) {
+         }));
+    CDA_TRY(comm_group("ncclReduce", [&](void* cv) {
              return (int)ncclReduce(err, err, 1, ncclUint32, ncclMin, 0, static_cast<ncclComm_t>(cv), s);
-         })))
-        return rc;
+         }));
     if (local != CDA_OK) return fail(local, local_msg);
     if (rank_ != 0) return CDA_OK;
     // 5. rank 0: a peer that failed left 0 in the reduced word -- nothing valid
     //    to combine; otherwise the top log2(G) levels of every row tree, the
     //    roots and the data root
     uint32_t word = 0;
-    if ((rc = check(hipMemcpyAsync(&word, err, 4, hipMemcpyDeviceToHost, s), "D2H push-order word"))) return rc;
+    CDA_TRY(d2h(&word, err, 4, s, "D2H push-order word"));
     const hipError_t se = hipStreamSynchronize(s);
     if (!comm_alive()) return aborted(*this, "ncclReduce");
-    if ((rc = check(se, "hipStreamSynchronize"))) return rc;
+    CDA_TRY(check(se, "hipStreamSynchronize"));
     if (word == 0)
         return fail(CDA_ERR_DEVICE,
                     "a peer rank failed its local stage (MIN-reduced push-order word 0): roots not written");

@@ -711,57 +711,54 @@ int Engine::enqueue_commitments(const square::CommitPlan& p, uint32_t n_blobs, c
     }
     const size_t gr_b = grp.size() * 4;
     const size_t plan_b = seg_b + st_b + bt_b + gr_b;
-    int rc;
-    if (sq_event_ && (rc = check(hipEventSynchronize(sq_event_), "hipEventSynchronize"))) return rc;
+    if (sq_event_) CDA_TRY(check(hipEventSynchronize(sq_event_), "hipEventSynchronize"));
     if (plan_b > sq_stage_bytes_) {
         if (sq_stage_) (void)hipHostFree(sq_stage_);
         sq_stage_ = nullptr;
         sq_stage_bytes_ = 0;
-        if ((rc = check(hipHostMalloc(&sq_stage_, plan_b, hipHostMallocDefault), "hipHostMalloc"))) return rc;
+        CDA_TRY(check(hipHostMalloc(&sq_stage_, plan_b, hipHostMallocDefault), "hipHostMalloc"));
         sq_stage_bytes_ = plan_b;
     }
-    if (!sq_event_ && (rc = check(hipEventCreateWithFlags(&sq_event_, hipEventDisableTiming), "hipEventCreate")))
-        return rc;
+    if (!sq_event_) CDA_TRY(check(hipEventCreateWithFlags(&sq_event_, hipEventDisableTiming), "hipEventCreate"));
     uint8_t* stage = static_cast<uint8_t*>(sq_stage_);
     if (seg_b) std::memcpy(stage, p.segs.data(), seg_b);
     if (st_b) std::memcpy(stage + seg_b, p.seg_tree0.data(), st_b);
     std::memcpy(stage + seg_b + st_b, p.blob_tree0.data(), bt_b);
     if (gr_b) std::memcpy(stage + seg_b + st_b + bt_b, grp.data(), gr_b);
-    if ((rc = check(cm_plan_.ensure(plan_b), "hipMalloc"))) return rc;
-    if ((rc = check(hipMemcpyAsync(cm_plan_.ptr, stage, plan_b, hipMemcpyHostToDevice, s), "H2D plan"))) return rc;
-    if ((rc = check(hipEventRecord(sq_event_, s), "hipEventRecord"))) return rc;
+    CDA_TRY(ensure(cm_plan_, plan_b, "hipMalloc"));
+    CDA_TRY(h2d(cm_plan_.ptr, stage, plan_b, s, "H2D plan"));
+    CDA_TRY(check(hipEventRecord(sq_event_, s), "hipEventRecord"));
     const square::Segment* d_segs = cm_plan_.as<square::Segment>();
     const uint32_t* d_st = reinterpret_cast<const uint32_t*>(cm_plan_.as<uint8_t>() + seg_b);
     const uint32_t* d_bt = reinterpret_cast<const uint32_t*>(cm_plan_.as<uint8_t>() + seg_b + st_b);
     const uint32_t* d_grp = reinterpret_cast<const uint32_t*>(cm_plan_.as<uint8_t>() + seg_b + st_b + bt_b);
     const uint32_t N = p.n_leaves, n_trees = p.n_trees;
     if (N) {
-        if ((rc = check(cm_leaf_.ensure((size_t)N * kSlot), "hipMalloc"))) return rc;
-        if ((rc = check(cm_lvl_.ensure((size_t)(N / 2 + 1) * kSlot), "hipMalloc"))) return rc;
-        if ((rc = check(cm_roots_.ensure((size_t)n_trees * 32), "hipMalloc"))) return rc;   // RFC leaf digests
-        if ((rc = check(cm_tables_.ensure((size_t)N * 4 + (size_t)n_trees * sizeof(Tree)), "hipMalloc"))) return rc;
+        CDA_TRY(ensure(cm_leaf_, (size_t)N * kSlot, "hipMalloc"));
+        CDA_TRY(ensure(cm_lvl_, (size_t)(N / 2 + 1) * kSlot, "hipMalloc"));
+        CDA_TRY(ensure(cm_roots_, (size_t)n_trees * 32, "hipMalloc"));   // RFC leaf digests
+        CDA_TRY(ensure(cm_tables_, (size_t)N * 4 + (size_t)n_trees * sizeof(Tree), "hipMalloc"));
         uint32_t* d_leaf_tree = cm_tables_.as<uint32_t>();
         Tree* d_trees = reinterpret_cast<Tree*>(d_leaf_tree + N);
         hipLaunchKernelGGL(blob_leaf_kernel, dim3((N + 255) / 256), dim3(256), 0, s, d_segs, (uint32_t)p.segs.size(),
                            d_st, d_trees, d_leaf_tree, d_data, cm_leaf_.as<uint8_t>(), N);
-        if ((rc = check(hipGetLastError(), "blob leaves"))) return rc;
+        CDA_TRY(launched("blob leaves"));
         if (fused) {
-            if (fused_lds > 48 * 1024 &&
-                (rc = check(hipFuncSetAttribute(reinterpret_cast<const void*>(commitment_fused_kernel),
-                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds),
-                            "hipFuncSetAttribute")))
-                return rc;
+            if (fused_lds > 48 * 1024)
+                CDA_TRY(check(hipFuncSetAttribute(reinterpret_cast<const void*>(commitment_fused_kernel),
+                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds),
+                              "hipFuncSetAttribute"));
             // lane pairs cut a compression's latency but cost 1.6x its lane
             // work: kept for when the groups leave most of the chip idle
             const uint32_t n_groups = (uint32_t)grp.size() - 1, pair_ok = n_groups <= 512 ? 1u : 0u;
             hipLaunchKernelGGL(commitment_fused_kernel, dim3(n_groups), dim3(256), fused_lds, s, cm_leaf_.as<uint8_t>(),
                                d_trees, d_leaf_tree, d_bt, d_grp, d_out, pair_ok);
-            return check(hipGetLastError(), "commitments");
+            return launched("commitments");
         }
         if (p.max_height == 0) {   // else the level-1 launch hashes the height-0 subtrees too
             hipLaunchKernelGGL(leaf_roots_kernel, dim3((n_trees + 255) / 256), dim3(256), 0, s, d_trees, n_trees,
                                cm_leaf_.as<uint8_t>(), cm_roots_.as<uint32_t>());
-            if ((rc = check(hipGetLastError(), "leaf roots"))) return rc;
+            CDA_TRY(launched("leaf roots"));
         }
         for (uint32_t L = 1; L <= p.max_height; L++) {
             uint8_t* in = (L - 1) % 2 == 0 ? cm_leaf_.as<uint8_t>() : cm_lvl_.as<uint8_t>();
@@ -770,43 +767,35 @@ int Engine::enqueue_commitments(const square::CommitPlan& p, uint32_t n_blobs, c
             const uint64_t threads = (uint64_t)n_nodes + (L == 1 ? n_trees : 0u);
             hipLaunchKernelGGL(subtree_level_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s, d_trees,
                                n_trees, d_leaf_tree, in, out, cm_roots_.as<uint32_t>(), L, n_nodes);
-            if ((rc = check(hipGetLastError(), "subtree level"))) return rc;
+            CDA_TRY(launched("subtree level"));
         }
     }
     if (!grp.empty()) {
         const size_t lds = (size_t)std::max(max_gt, 1u) * 32;
         if (lds > 159 * 1024) return fail(CDA_ERR_UNSUPPORTED, "too many subtree roots in one blob");
-        if (lds > 64 * 1024 &&
-            (rc = check(hipFuncSetAttribute(reinterpret_cast<const void*>(commitment_group_kernel),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        "hipFuncSetAttribute")))
-            return rc;
+        if (lds > 64 * 1024) CDA_TRY(check(hipFuncSetAttribute(reinterpret_cast<const void*>(commitment_group_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute"));
         hipLaunchKernelGGL(commitment_group_kernel, dim3((uint32_t)grp.size() - 1), dim3(64), lds, s,
                            cm_roots_.as<uint32_t>(), d_bt, d_grp, d_out);
-        return check(hipGetLastError(), "commitments");
+        return launched("commitments");
     }
     const uint32_t mt = p.max_trees ? p.max_trees : 1;
     const size_t lds = (size_t)(mt + (mt + 1) / 2) * 32;
     if (lds > 160 * 1024) return fail(CDA_ERR_UNSUPPORTED, "too many subtree roots in one blob");
-    if (lds > 64 * 1024 &&
-        (rc = check(hipFuncSetAttribute(reinterpret_cast<const void*>(commitment_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                    "hipFuncSetAttribute")))
-        return rc;
+    if (lds > 64 * 1024) CDA_TRY(check(hipFuncSetAttribute(reinterpret_cast<const void*>(commitment_kernel),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute"));
     hipLaunchKernelGGL(commitment_kernel, dim3(n_blobs), dim3(64), lds, s, cm_roots_.as<uint32_t>(), d_bt, mt, d_out);
-    return check(hipGetLastError(), "commitments");
+    return launched("commitments");
 }
 
 int Engine::host_commitments(const square::CommitPlan& p, uint32_t n_blobs, const uint8_t* data, size_t data_len,
                              uint8_t* out) {
     hipStream_t s = stream_;
-    int rc;
-    if ((rc = upload_txs(data, data_len, s))) return rc;
-    if ((rc = check(cm_out_.ensure((size_t)n_blobs * 32), "hipMalloc"))) return rc;
-    if ((rc = enqueue_commitments(p, n_blobs, sq_txs_.as<uint8_t>(), cm_out_.as<uint8_t>(), s))) return rc;
-    if ((rc = check(hipMemcpyAsync(out, cm_out_.ptr, (size_t)n_blobs * 32, hipMemcpyDeviceToHost, s), "D2H")))
-        return rc;
-    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    CDA_TRY(upload_txs(data, data_len, s));
+    CDA_TRY(ensure(cm_out_, (size_t)n_blobs * 32, "hipMalloc"));
+    CDA_TRY(enqueue_commitments(p, n_blobs, sq_txs_.as<uint8_t>(), cm_out_.as<uint8_t>(), s));
+    CDA_TRY(d2h(out, cm_out_.ptr, (size_t)n_blobs * 32, s, "D2H"));
+    return sync(s);
 }
 
 }  // namespace cda

@@ -17,7 +17,18 @@
 
 struct cda_share_proof_batch;   // include/cda.h
 
+// The one early-return form of the host code: a non-zero CDA_* code leaves the function.
+#define CDA_TRY(expr)                     \
+    do {                                  \
+        if (int rc_ = (expr)) return rc_; \
+    } while (0)
+
 namespace cda {
+
+// sha256(""): merkle.HashFromByteSlices(nil), and the digest of NmtHasher.EmptyRoot
+inline constexpr uint8_t kSha256Empty[32] = {0xe3, 0xb0, 0xc4, 0x42, 0x98, 0xfc, 0x1c, 0x14, 0x9a, 0xfb, 0xf4,
+                                             0xc8, 0x99, 0x6f, 0xb9, 0x24, 0x27, 0xae, 0x41, 0xe4, 0x64, 0x9b,
+                                             0x93, 0x4c, 0xa4, 0x95, 0x99, 0x1b, 0x78, 0x52, 0xb8, 0x55};
 
 // Page-locks a caller's host buffer for the duration of a call (RAII), so
 // its copies are plain DMA: both PCIe directions then run at once (a pageable
@@ -96,7 +107,7 @@ hipError_t launch_slot_merkle_roots(const uint8_t* slots, const uint32_t* bt, ui
 // all RFC-6962 levels of the data-root tree.
 struct ResidentSquare {
     enum Part { kRowRoots, kColRoots, kDataRoot, kEds };
-    uint32_t k = 0, log_w = 0, push_err = 0xFFFFFFFFu;
+    uint32_t k = 0, log_w = 0, push_err = push_order::kOrdered;
     DevBuf eds, levels, col_levels, roots_slots, rfc, rows, cols, root, err, scratch, pieces;
     uint64_t level_offset(uint32_t L) const;       // bytes into `levels`, L >= 0
     uint64_t col_level_offset(uint32_t L) const;   // bytes into `col_levels`, L >= 1
@@ -321,6 +332,20 @@ class Engine {
 
   private:
     int check(hipError_t e, const char* what);
+    // Staging helpers: one HIP call each, its result and the caller's stage
+    // string handed to check().  They add, merge and reorder nothing.
+    int ensure(DevBuf& b, size_t n, const char* what) { return check(b.ensure(n), what); }
+    int h2d(void* dst, const void* src, size_t n, hipStream_t s, const char* what) {
+        return check(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s), what);
+    }
+    int d2h(void* dst, const void* src, size_t n, hipStream_t s, const char* what) {
+        return check(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s), what);
+    }
+    int fill(void* p, int v, size_t n, hipStream_t s, const char* what) {
+        return check(hipMemsetAsync(p, v, n, s), what);
+    }
+    int launched(const char* what) { return check(hipGetLastError(), what); }   // after a <<<>>> launch
+    int sync(hipStream_t s, const char* what = "hipStreamSynchronize") { return check(hipStreamSynchronize(s), what); }
     // stages enqueued since the context's work was last seen complete (for
     // attributing asynchronous device faults; see check())
     static constexpr size_t kMaxPending = 48;
@@ -343,8 +368,15 @@ class Engine {
     uint32_t top_fuse_nodes(uint32_t W, uint32_t n, bool* wide = nullptr) const;
     int top_fuse_ = -1;   // CDA_TOP_FUSE (tuning / A-B): -1 auto, 0 off, N = nodes per tree
     int top_wide_ = 2;    // CDA_TOP_WIDE: levels the tree top absorbs below the lane-pair level
+    int check_width(uint32_t k);   // CDA_ERR_INVALID unless k is a power of two <= 1024
+    // The reference's ErrInvalidPushOrder text from the two namespaces (NULL: a
+    // parity cell's, all 0xFF), and the one for the first violating square of
+    // a batch's push-order words (push_order.h), which also sets po_*.
+    int fail_push_order(const uint8_t* last_ns, const uint8_t* pushed_ns);
     int push_order_error(const uint32_t* err_words, uint32_t n, const uint8_t* host_q0_src, uint32_t k,
                          bool src_is_eds);
+    // n push-order words of finished work on s: D2H, then the wait
+    int read_push_order(const void* d_words, uint32_t n, uint32_t* words, hipStream_t s);
     std::string fault_;   // CDA_FAULT (tests only)
 
     struct Mark {
@@ -380,6 +412,15 @@ class Engine {
     uint32_t host_pipe_chunk_ = 0;   // CDA_HOST_PIPE_CHUNK: squares per chunk (0 = auto: ~256 MiB of ODS)
     int host_pipeline(const uint8_t* ods, uint32_t k, uint32_t n, uint8_t* eds, uint8_t* rows, uint8_t* cols,
                       uint8_t* roots, int32_t* status, uint32_t chunk, int eds_mode);
+    // Head and tail of the host-buffer batch paths (host_extend_dah,
+    // host_pipeline, host_dah).  host_stage: the device staging, `resident`
+    // squares of ODS / EDS / (packed) parity and the n squares' roots and
+    // push-order words.  host_finish: roots and words back on stream_, Q0
+    // copied on the host meanwhile (q0_eds, or NULL), the wait for stream_ and
+    // the caller's own wait for its parity copies (or none), status, error text.
+    int host_stage(uint32_t k, uint32_t n, uint32_t resident, bool ods, bool packed);
+    int host_finish(const uint8_t* src, bool src_is_eds, uint32_t k, uint32_t n, uint8_t* q0_eds, uint8_t* rows,
+                    uint8_t* cols, uint8_t* roots, int32_t* status, const std::function<int()>& parity_wait);
     DevBuf h_par_;   // packed-parity staging (eds_mode PARITY)
     static void copy_q0(const uint8_t* ods, uint32_t k, uint32_t n, uint8_t* eds);
     hipEvent_t order_ev_ = nullptr;   // end of the last call's GPU work

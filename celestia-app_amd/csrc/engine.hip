@@ -25,6 +25,7 @@
 #include "leopard_tables.h"
 #include "sha256_dev.h"
 #include "split_layout.h"
+#include "tree_index.h"
 
 namespace cda {
 
@@ -199,24 +200,22 @@ int Engine::init() {
         if (hipGetDevice(&device_) != hipSuccess) return fail(CDA_ERR_DEVICE, "hipGetDevice failed");
     }
     if (device_ >= n) return fail(CDA_ERR_INVALID, "device ordinal out of range");
-    int rc;
-    if ((rc = check(hipSetDevice(device_), "hipSetDevice"))) return rc;
-    if ((rc = check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
-    if ((rc = check(hipEventCreateWithFlags(&order_ev_, hipEventDisableTiming), "hipEventCreate"))) return rc;
-    if ((rc = check(hipStreamCreateWithFlags(&copy_out_, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
-    if ((rc = check(hipEventCreateWithFlags(&ev_rs_, hipEventDisableTiming), "hipEventCreate"))) return rc;
-    if ((rc = check(hipEventCreateWithFlags(&ev_out_, hipEventDisableTiming), "hipEventCreate"))) return rc;
-    if ((rc = check(hipStreamCreateWithFlags(&copy_in_, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
+    CDA_TRY(check(hipSetDevice(device_), "hipSetDevice"));
+    CDA_TRY(check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate"));
+    CDA_TRY(check(hipEventCreateWithFlags(&order_ev_, hipEventDisableTiming), "hipEventCreate"));
+    CDA_TRY(check(hipStreamCreateWithFlags(&copy_out_, hipStreamNonBlocking), "hipStreamCreate"));
+    CDA_TRY(check(hipEventCreateWithFlags(&ev_rs_, hipEventDisableTiming), "hipEventCreate"));
+    CDA_TRY(check(hipEventCreateWithFlags(&ev_out_, hipEventDisableTiming), "hipEventCreate"));
+    CDA_TRY(check(hipStreamCreateWithFlags(&copy_in_, hipStreamNonBlocking), "hipStreamCreate"));
     for (hipEvent_t* e : {pipe_in_, pipe_rs_, pipe_d2h_, pipe_comp_})
         for (uint32_t i = 0; i < kPipeSlots; i++)
-            if ((rc = check(hipEventCreateWithFlags(&e[i], hipEventDisableTiming), "hipEventCreate"))) return rc;
+            CDA_TRY(check(hipEventCreateWithFlags(&e[i], hipEventDisableTiming), "hipEventCreate"));
     // CDA_RS_PRIORITY (tuning): priority of the pipeline's RS stream (HIP: a
     // lower value is a higher priority).
     if (const char* env = test_knob("CDA_RS_PRIORITY")) {
-        if ((rc = check(hipStreamCreateWithPriority(&aux_stream_, hipStreamNonBlocking, atoi(env)), "hipStreamCreate")))
-            return rc;
-    } else if ((rc = check(hipStreamCreateWithFlags(&aux_stream_, hipStreamNonBlocking), "hipStreamCreate"))) {
-        return rc;
+        CDA_TRY(check(hipStreamCreateWithPriority(&aux_stream_, hipStreamNonBlocking, atoi(env)), "hipStreamCreate"));
+    } else {
+        CDA_TRY(check(hipStreamCreateWithFlags(&aux_stream_, hipStreamNonBlocking), "hipStreamCreate"));
     }
     if (const char* env = deploy_knob("CDA_PIPELINE_CHUNK")) pipeline_chunk_ = (uint32_t)strtoul(env, nullptr, 10);
     if (const char* env = test_knob("CDA_HASH_SPLIT")) hash_split_ = atoi(env);
@@ -236,13 +235,12 @@ int Engine::init() {
     // GF(2^16) tables (leopard.go initLUTs / initFFT), built on the host once.
     auto F = std::make_unique<LeoField<16>>();
     leo_build<16>(*F, 0x1002D, kCantor16);
-    if ((rc = check(gf16_log_.ensure_fixed(sizeof F->log), "hipMalloc"))) return rc;
-    if ((rc = check(gf16_exp_.ensure_fixed(sizeof F->exp), "hipMalloc"))) return rc;
-    if ((rc = check(gf16_skew_.ensure_fixed(sizeof F->skew), "hipMalloc"))) return rc;
-    if ((rc = check(hipMemcpy(gf16_log_.ptr, F->log, sizeof F->log, hipMemcpyHostToDevice), "hipMemcpy"))) return rc;
-    if ((rc = check(hipMemcpy(gf16_exp_.ptr, F->exp, sizeof F->exp, hipMemcpyHostToDevice), "hipMemcpy"))) return rc;
-    if ((rc = check(hipMemcpy(gf16_skew_.ptr, F->skew, sizeof F->skew, hipMemcpyHostToDevice), "hipMemcpy")))
-        return rc;
+    CDA_TRY(check(gf16_log_.ensure_fixed(sizeof F->log), "hipMalloc"));
+    CDA_TRY(check(gf16_exp_.ensure_fixed(sizeof F->exp), "hipMalloc"));
+    CDA_TRY(check(gf16_skew_.ensure_fixed(sizeof F->skew), "hipMalloc"));
+    CDA_TRY(check(hipMemcpy(gf16_log_.ptr, F->log, sizeof F->log, hipMemcpyHostToDevice), "hipMemcpy"));
+    CDA_TRY(check(hipMemcpy(gf16_exp_.ptr, F->exp, sizeof F->exp, hipMemcpyHostToDevice), "hipMemcpy"));
+    CDA_TRY(check(hipMemcpy(gf16_skew_.ptr, F->skew, sizeof F->skew, hipMemcpyHostToDevice), "hipMemcpy"));
     return CDA_OK;
 }
 
@@ -251,7 +249,9 @@ Gf16Dev Engine::gf16(uint32_t k) const {
     return Gf16Dev{gf16_log_.as<uint16_t>(), gf16_exp_.as<uint16_t>(), gf16_skew_.as<uint16_t>()};
 }
 
-static bool pow2(uint64_t x) { return x && !(x & (x - 1)); }
+int Engine::check_width(uint32_t k) {
+    return is_pow2(k) && k <= 1024 ? CDA_OK : fail(CDA_ERR_INVALID, "square width must be a power of two <= 1024");
+}
 
 static_assert(kPlanSlot == (uint32_t)kSlot, "hash_plan.h plans scratch in node slots");
 
@@ -355,8 +355,7 @@ int Engine::collect_stage_times(double* ms, uint32_t* counts, int n) {
 
 int Engine::enqueue_extend(const uint8_t* d_ods, uint32_t k, uint32_t n, uint8_t* d_eds, hipStream_t s,
                            uint32_t* err_init) {
-    if (!pow2(k) || k > 1024) return fail(CDA_ERR_INVALID, "square width must be a power of two <= 1024");
-    int rc;
+    CDA_TRY(check_width(k));
     const Gf16Dev t = gf16(k);
     mark_begin(kStageRsQ0, s);
     // d_ods == NULL: in place, the ODS is already in Q0 of d_eds
@@ -364,10 +363,10 @@ int Engine::enqueue_extend(const uint8_t* d_ods, uint32_t k, uint32_t n, uint8_t
     RsJob q3 = square_job_q3(d_eds, k);
     q0.err_init = err_init;
     q0.prio = q3.prio = (k >= 256 ? n <= rs16_prio_max_ : rs8_prio_) ? 1u : 0u;
-    if ((rc = check(launch_rs(q0, k, n, t, s), "rs Q0"))) return rc;
+    CDA_TRY(check(launch_rs(q0, k, n, t, s), "rs Q0"));
     mark_end(s);
     mark_begin(kStageRsQ3, s);
-    if ((rc = check(launch_rs(q3, k, n, t, s), "rs Q3"))) return rc;
+    CDA_TRY(check(launch_rs(q3, k, n, t, s), "rs Q3"));
     mark_end(s);
     return CDA_OK;
 }
@@ -377,7 +376,6 @@ int Engine::enqueue_extend(const uint8_t* d_ods, uint32_t k, uint32_t n, uint8_t
 int Engine::run_forests(Forest* f, uint32_t n_forest, uint32_t n_in, uint32_t n, uint8_t* bufA, uint8_t* bufB,
                         uint64_t buf_sq, const uint64_t* out_off, hipStream_t s, uint32_t stop, bool subtrees) {
     uint8_t* out = bufA;
-    int rc;
     // The first levels as one fused subtree launch (nmt.hip subtree_kernel):
     // a lane per (n_in / sub)-leaf subtree, sub the smallest node count >= stop
     // at which the launch holds `want` lanes (default two waves per
@@ -410,7 +408,7 @@ int Engine::run_forests(Forest* f, uint32_t n_forest, uint32_t n_in, uint32_t n,
                 f[i].out = out + out_off[i];
                 f[i].out_sq = buf_sq;
             }
-            if ((rc = check(launch_subtrees(f, n_forest, n_in, sub, n, s), "nmt subtrees"))) return rc;
+            CDA_TRY(check(launch_subtrees(f, n_forest, n_in, sub, n, s), "nmt subtrees"));
             for (uint32_t i = 0; i < n_forest; i++) {
                 f[i].in = out + out_off[i];
                 f[i].in_sq = buf_sq;
@@ -426,7 +424,7 @@ int Engine::run_forests(Forest* f, uint32_t n_forest, uint32_t n_in, uint32_t n,
             f[i].out = out + out_off[i];
             f[i].out_sq = buf_sq;
         }
-        if ((rc = check(launch_level(f, n_forest, m, n, s), "nmt level"))) return rc;
+        CDA_TRY(check(launch_level(f, n_forest, m, n, s), "nmt level"));
         for (uint32_t i = 0; i < n_forest; i++) {   // next level reads this one
             f[i].in = out + out_off[i];
             f[i].in_sq = buf_sq;
@@ -445,19 +443,17 @@ int Engine::run_forests(Forest* f, uint32_t n_forest, uint32_t n_in, uint32_t n,
 // d_err == NULL: the push-order words are already set (enqueue_extend's err_init).
 int Engine::dah_prepare(uint32_t W, uint32_t n, uint32_t* d_err, hipStream_t s) {
     const uint64_t slots_sq = (uint64_t)W * W * kSlot;
-    int rc;
-    if ((rc = check(leaf_.ensure(slots_sq * n), "hipMalloc leaf slots"))) return rc;
-    if ((rc = check(lvl_.ensure(slots_sq * n), "hipMalloc level slots"))) return rc;
-    if ((rc = check(root_slots_.ensure((size_t)n * 2 * W * kSlot), "hipMalloc root slots"))) return rc;
-    if ((rc = check(dig_.ensure((size_t)n * 2 * W * 32), "hipMalloc digests"))) return rc;
-    return d_err ? check(hipMemsetAsync(d_err, 0xFF, (size_t)n * 4, s), "hipMemsetAsync") : CDA_OK;
+    CDA_TRY(ensure(leaf_, slots_sq * n, "hipMalloc leaf slots"));
+    CDA_TRY(ensure(lvl_, slots_sq * n, "hipMalloc level slots"));
+    CDA_TRY(ensure(root_slots_, (size_t)n * 2 * W * kSlot, "hipMalloc root slots"));
+    CDA_TRY(ensure(dig_, (size_t)n * 2 * W * 32, "hipMalloc digests"));
+    return d_err ? fill(d_err, 0xFF, (size_t)n * 4, s, "hipMemsetAsync") : CDA_OK;
 }
 
 int Engine::reserve(uint32_t k, uint32_t n) {
-    int rc;
     if (!err_words(n)) return fail(CDA_ERR_OOM, "hipMalloc err words");
-    if ((rc = dah_prepare(2 * k, n, nullptr, stream_))) return rc;
-    return check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    CDA_TRY(dah_prepare(2 * k, n, nullptr, stream_));
+    return sync(stream_);
 }
 
 // Row trees: leaves (t, i); column trees: leaves (i, t) of the same leaf grid.
@@ -478,25 +474,16 @@ int Engine::dah_chunk(const uint8_t* d_eds, uint32_t k, uint32_t i0, uint32_t m,
                       const Forest (&f)[2], Forest (&post)[2], hipStream_t s, bool subtrees) {
     const uint32_t W = 2 * k;
     const uint64_t slots_sq = (uint64_t)W * W * kSlot, eds_sq = (uint64_t)W * W * kShare;
-    int rc;
     mark_begin(kStageLeaves, s);
     const CellGrid g{d_eds + i0 * eds_sq, eds_sq, W, W, W, 0, 0, k};
-    if ((rc = check(launch_leaves(g, m, leaf_.as<uint8_t>() + i0 * slots_sq, d_err + i0, true, true, s),
-                    "leaf hashing")))
-        return rc;
+    CDA_TRY(check(launch_leaves(g, m, leaf_.as<uint8_t>() + i0 * slots_sq, d_err + i0, true, true, s), "leaf hashing"));
     mark_end(s);
-    Forest fc[2] = {f[0], f[1]};
-    for (int i = 0; i < 2; i++) {
-        fc[i].in += i0 * fc[i].in_sq;
-        if (fc[i].roots) fc[i].roots += i0 * fc[i].roots_sq;
-        if (fc[i].root_slots) fc[i].root_slots += i0 * fc[i].rslot_sq;
-    }
+    Forest fc[2] = {f[0].from_square(i0), f[1].from_square(i0)};
     if (W > stop) {
         mark_begin(kStageLevels, s);
         const uint64_t off[2] = {0, slots_sq / 2};
-        if ((rc = run_forests(fc, 2, W, m, lvl_.as<uint8_t>() + i0 * slots_sq, leaf_.as<uint8_t>() + i0 * slots_sq,
-                              slots_sq, off, s, stop, subtrees)))
-            return rc;
+        CDA_TRY(run_forests(fc, 2, W, m, lvl_.as<uint8_t>() + i0 * slots_sq, leaf_.as<uint8_t>() + i0 * slots_sq,
+                slots_sq, off, s, stop, subtrees));
         mark_end(s);
     }
     for (int i = 0; i < 2; i++) {
@@ -515,13 +502,7 @@ int Engine::dah_finish(uint32_t k, uint32_t i0, uint32_t n, uint32_t from, const
                        uint32_t* d_err, int32_t* d_status, hipStream_t s) {
     const uint32_t W = 2 * k;
     const uint64_t slots_sq = (uint64_t)W * W * kSlot;
-    int rc;
-    Forest f[2] = {fb[0], fb[1]};
-    for (int i = 0; i < 2; i++) {
-        f[i].in += i0 * f[i].in_sq;
-        if (f[i].roots) f[i].roots += i0 * f[i].roots_sq;
-        if (f[i].root_slots) f[i].root_slots += i0 * f[i].rslot_sq;
-    }
+    Forest f[2] = {fb[0].from_square(i0), fb[1].from_square(i0)};
     uint32_t* dig = dig_.as<uint32_t>() + (size_t)i0 * 2 * W * 8;
     uint8_t* rslots = root_slots_.as<uint8_t>() + (size_t)i0 * 2 * W * kSlot;
     if (d_roots) d_roots += (size_t)i0 * 32;
@@ -544,35 +525,32 @@ int Engine::dah_finish(uint32_t k, uint32_t i0, uint32_t n, uint32_t from, const
             uint8_t* a = (in_lvl ? leaf_.as<uint8_t>() : lvl_.as<uint8_t>()) + i0 * slots_sq;
             uint8_t* b = (in_lvl ? lvl_.as<uint8_t>() : leaf_.as<uint8_t>()) + i0 * slots_sq;
             const uint64_t off[2] = {0, slots_sq / 2};
-            if ((rc = run_forests(f, 2, from, n, a, b, slots_sq, off, s, stop))) return rc;
+            CDA_TRY(run_forests(f, 2, from, n, a, b, slots_sq, off, s, stop));
         }
-        if (top && (rc = check(launch_tree_top(f, 2, top, n, d_roots ? dig : nullptr, 2 * W, s, &n_dig, wide),
-                               "nmt tree top")))
-            return rc;
+        if (top) CDA_TRY(check(launch_tree_top(f, 2, top, n, d_roots ? dig : nullptr, 2 * W, s, &n_dig, wide),
+                         "nmt tree top"));
         mark_end(s);
     }
     // the data-root launch also writes the per-square push-order status
     if (d_roots && top) {
         mark_begin(kStageDataRoot, s);
-        if ((rc = check(launch_data_root_digests(dig, n_dig, n, d_roots, s, d_err, d_status), "data root")))
-            return rc;
+        CDA_TRY(check(launch_data_root_digests(dig, n_dig, n, d_roots, s, d_err, d_status), "data root"));
         mark_end(s);
     } else if (d_roots) {   // NULL: roots only (repair verification needs no data root)
         mark_begin(kStageDataRoot, s);
-        if ((rc = check(launch_data_root_slots(rslots, 2 * W, n, dig, d_roots, s, d_err, d_status), "data root")))
-            return rc;
+        CDA_TRY(check(launch_data_root_slots(rslots, 2 * W, n, dig, d_roots, s, d_err, d_status), "data root"));
         mark_end(s);
     }
-    if (!d_roots && d_status && (rc = check(launch_status(d_err, n, d_status, s), "status"))) return rc;
+    if (!d_roots && d_status) CDA_TRY(check(launch_status(d_err, n, d_status, s), "status"));
     return CDA_OK;
 }
 
 int Engine::enqueue_dah(const uint8_t* d_eds, uint32_t k, uint32_t n, uint8_t* d_rows, uint8_t* d_cols,
                         uint8_t* d_roots, uint32_t* d_err, int32_t* d_status, hipStream_t s, bool err_ready) {
-    if (!pow2(k) || k > 1024) return fail(CDA_ERR_INVALID, "square width must be a power of two <= 1024");
+    CDA_TRY(check_width(k));
     const uint32_t W = 2 * k;
     int rc;
-    if ((rc = dah_prepare(W, n, err_ready ? nullptr : d_err, s))) return rc;
+    CDA_TRY(dah_prepare(W, n, err_ready ? nullptr : d_err, s));
     Forest f[2], post[2];
     dah_forests(W, d_rows, d_cols, f);
     const uint32_t top = top_fuse_nodes(W, n);
@@ -601,7 +579,7 @@ int Engine::enqueue_dah(const uint8_t* d_eds, uint32_t k, uint32_t n, uint8_t* d
     if (parts > 1) {
         hipEvent_t go = sync_event(0);
         if (!go || !sync_event(parts)) return fail(CDA_ERR_DEVICE, "hipEventCreate failed");
-        if ((rc = check(hipEventRecord(go, s), "hipEventRecord"))) return rc;
+        CDA_TRY(check(hipEventRecord(go, s), "hipEventRecord"));
         // part p: squares [p n / parts, (p + 1) n / parts); part 0 on the
         // caller's stream.  Each part also finishes its own trees and data
         // roots, so one part's latency-bound data root runs under another's
@@ -653,7 +631,7 @@ int Engine::enqueue_dah(const uint8_t* d_eds, uint32_t k, uint32_t n, uint8_t* d
         }
         return err;
     }
-    if ((rc = dah_chunk(d_eds, k, 0, n, stop, d_err, f, post, s, true))) return rc;
+    CDA_TRY(dah_chunk(d_eds, k, 0, n, stop, d_err, f, post, s, true));
     return dah_finish(k, 0, n, stop, post, d_roots, d_err, d_status, s);
 }
 
@@ -662,12 +640,11 @@ int Engine::enqueue_dah(const uint8_t* d_eds, uint32_t k, uint32_t n, uint8_t* d
 // ---------------------------------------------------------------------------
 int Engine::enqueue_split_rows(const uint8_t* d_rows, uint32_t k, uint32_t n_rows, uint32_t row0, uint8_t* d_block,
                                uint32_t* d_err, hipStream_t s) {
-    if (!pow2(k) || k > 1024 || n_rows == 0 || row0 + n_rows > k)
+    if (!is_pow2(k) || k > 1024 || n_rows == 0 || row0 + n_rows > k)
         return fail(CDA_ERR_INVALID, "bad row block");
     const uint32_t W = 2 * k, SH = kShare;
-    int rc;
     const CellGrid g{d_rows, 0, n_rows, k, k, row0, 0, k};
-    if ((rc = check(launch_row_order(g, 1, d_err, s), "row order"))) return rc;
+    CDA_TRY(check(launch_row_order(g, 1, d_err, s), "row order"));
     RsJob j{};
     j.src = d_rows;
     j.dst = d_block;
@@ -679,26 +656,24 @@ int Engine::enqueue_split_rows(const uint8_t* d_rows, uint32_t k, uint32_t n_row
 int Engine::enqueue_split_cols(uint8_t* d_block, uint32_t k, uint32_t n_cols, uint32_t col0, uint8_t* d_col_slots,
                                uint8_t* d_row_sub, uint32_t* d_err, hipStream_t s) {
     const uint32_t W = 2 * k, SH = kShare;
-    if (!pow2(k) || k > 1024 || !pow2(n_cols) || n_cols < 2 || col0 + n_cols > W)
+    if (!is_pow2(k) || k > 1024 || !is_pow2(n_cols) || n_cols < 2 || col0 + n_cols > W)
         return fail(CDA_ERR_INVALID, "bad column block");
-    int rc;
     RsJob j{};
     j.src = d_block;
     j.dst = d_block;
     j.n_seg = 1;
     j.seg[0] = RsSeg{n_cols, 0, SH, n_cols * SH, k * n_cols * SH, SH, n_cols * SH};
-    if ((rc = check(launch_rs(j, k, 1, gf16(k), s), "rs cols"))) return rc;
+    CDA_TRY(check(launch_rs(j, k, 1, gf16(k), s), "rs cols"));
     const uint64_t slots = (uint64_t)W * n_cols * kSlot;
-    if ((rc = check(leaf_.ensure(slots), "hipMalloc leaf slots"))) return rc;
-    if ((rc = check(lvl_.ensure(slots), "hipMalloc level slots"))) return rc;
+    CDA_TRY(ensure(leaf_, slots, "hipMalloc leaf slots"));
+    CDA_TRY(ensure(lvl_, slots, "hipMalloc level slots"));
     const CellGrid g{d_block, 0, W, n_cols, n_cols, 0, col0, k};
-    if ((rc = check(launch_leaves(g, 1, leaf_.as<uint8_t>(), d_err, true, true, s), "leaf hashing"))) return rc;
+    CDA_TRY(check(launch_leaves(g, 1, leaf_.as<uint8_t>(), d_err, true, true, s), "leaf hashing"));
     // row subtrees: W trees of n_cols leaves -> one 96-B slot per row
     // (ping-pong between the two halves of the level buffer; leaves untouched)
     Forest fr{leaf_.as<uint8_t>(), 0, W, n_cols, 1, nullptr, 0, nullptr, 0, d_row_sub, 0, 0};
     const uint64_t off0[1] = {0};
-    if ((rc = run_forests(&fr, 1, n_cols, 1, lvl_.as<uint8_t>(), lvl_.as<uint8_t>() + slots / 2, 0, off0, s)))
-        return rc;
+    CDA_TRY(run_forests(&fr, 1, n_cols, 1, lvl_.as<uint8_t>(), lvl_.as<uint8_t>() + slots / 2, 0, off0, s));
     // column trees: n_cols trees of W leaves; after their first level the leaf
     // buffer is free and becomes the second ping-pong buffer
     Forest fc{leaf_.as<uint8_t>(), 0, n_cols, 1, n_cols, nullptr, 0, nullptr, 0, d_col_slots, 0, 0};
@@ -708,15 +683,13 @@ int Engine::enqueue_split_cols(uint8_t* d_block, uint32_t k, uint32_t n_cols, ui
 int Engine::enqueue_split_combine(const uint8_t* d_row_sub, uint32_t parts, uint32_t k, const uint8_t* d_col_slots,
                                   uint8_t* d_rows, uint8_t* d_cols, uint8_t* d_root, hipStream_t s) {
     const uint32_t W = 2 * k;
-    if (!pow2(k) || !pow2(parts) || parts > W) return fail(CDA_ERR_INVALID, "bad split");
-    int rc;
-    if ((rc = check(root_slots_.ensure((size_t)2 * W * kSlot), "hipMalloc root slots"))) return rc;
-    if ((rc = check(lvl_.ensure((size_t)W * parts * kSlot), "hipMalloc level slots"))) return rc;
-    if ((rc = check(leaf_.ensure((size_t)W * parts * kSlot), "hipMalloc leaf slots"))) return rc;
+    if (!is_pow2(k) || !is_pow2(parts) || parts > W) return fail(CDA_ERR_INVALID, "bad split");
+    CDA_TRY(ensure(root_slots_, (size_t)2 * W * kSlot, "hipMalloc root slots"));
+    CDA_TRY(ensure(lvl_, (size_t)W * parts * kSlot, "hipMalloc level slots"));
+    CDA_TRY(ensure(leaf_, (size_t)W * parts * kSlot, "hipMalloc leaf slots"));
     uint8_t* rs = root_slots_.as<uint8_t>();
     if (parts == 1) {
-        if ((rc = check(hipMemcpyAsync(rs, d_row_sub, (size_t)W * kSlot, hipMemcpyDeviceToDevice, s), "copy")))
-            return rc;
+        CDA_TRY(check(hipMemcpyAsync(rs, d_row_sub, (size_t)W * kSlot, hipMemcpyDeviceToDevice, s), "copy"));
     } else {
         // row tree r: nodes (g, r) of the gathered [parts][W] -> top
         // log2(parts) levels (SplitLayout::combine_slot: tree stride 1, node stride W)
@@ -725,12 +698,11 @@ int Engine::enqueue_split_combine(const uint8_t* d_row_sub, uint32_t parts, uint
         const uint32_t nstride = (uint32_t)(L.combine_slot(1, 0) - L.combine_slot(0, 0));
         Forest fr{d_row_sub, 0, W, tstride, nstride, nullptr, 0, nullptr, 0, rs, 0, 0};
         const uint64_t off0[1] = {0};
-        if ((rc = run_forests(&fr, 1, parts, 1, lvl_.as<uint8_t>(), leaf_.as<uint8_t>(), 0, off0, s))) return rc;
+        CDA_TRY(run_forests(&fr, 1, parts, 1, lvl_.as<uint8_t>(), leaf_.as<uint8_t>(), 0, off0, s));
     }
-    if ((rc = check(hipMemcpyAsync(rs + (size_t)W * kSlot, d_col_slots, (size_t)W * kSlot, hipMemcpyDeviceToDevice, s),
-                    "copy")))
-        return rc;
-    if ((rc = check(launch_slots_to_roots(rs, 2 * W, d_rows, d_cols, W, s), "pack roots"))) return rc;
+    CDA_TRY(check(hipMemcpyAsync(rs + (size_t)W * kSlot, d_col_slots, (size_t)W * kSlot, hipMemcpyDeviceToDevice, s),
+            "copy"));
+    CDA_TRY(check(launch_slots_to_roots(rs, 2 * W, d_rows, d_cols, W, s), "pack roots"));
     return check(launch_data_root(rs, 2 * W, 1, d_root, s), "data root");
 }
 
@@ -752,8 +724,7 @@ int Engine::split_stream(uint32_t i, hipStream_t* out) {
     }
     hipStream_t& q = split_streams_[i - 1];
     if (!q) {
-        int rc;
-        if ((rc = check(hipStreamCreateWithFlags(&q, hipStreamNonBlocking), "hipStreamCreate"))) return rc;
+        CDA_TRY(check(hipStreamCreateWithFlags(&q, hipStreamNonBlocking), "hipStreamCreate"));
     }
     *out = q;
     return CDA_OK;
@@ -783,9 +754,7 @@ int Engine::make_cu_streams() {
     }
     for (int b = 0; b < ncu; b++)
         if (!(rs[b / 32] >> (b % 32) & 1)) hs[b / 32] |= 1u << (b % 32);
-    int rc;
-    if ((rc = check(hipExtStreamCreateWithCUMask(&rs_cu_stream_, (uint32_t)rs.size(), rs.data()), "cu mask stream")))
-        return rc;
+    CDA_TRY(check(hipExtStreamCreateWithCUMask(&rs_cu_stream_, (uint32_t)rs.size(), rs.data()), "cu mask stream"));
     return check(hipExtStreamCreateWithCUMask(&hash_cu_stream_, (uint32_t)hs.size(), hs.data()), "cu mask stream");
 }
 
@@ -802,7 +771,7 @@ int Engine::make_cu_streams() {
 int Engine::enqueue_extend_dah(const uint8_t* d_ods, uint32_t k, uint32_t n, uint8_t* d_eds, uint8_t* d_rows,
                                uint8_t* d_cols, uint8_t* d_roots, uint32_t* d_err, int32_t* d_status,
                                hipStream_t s) {
-    if (!pow2(k) || k > 1024) return fail(CDA_ERR_INVALID, "square width must be a power of two <= 1024");
+    CDA_TRY(check_width(k));
     const uint32_t c = pipeline_chunk_ ? pipeline_chunk_ : n;
     if (c >= n) return enqueue_extend_dah_serial(d_ods, k, n, d_eds, d_rows, d_cols, d_roots, d_err, d_status, s);
     const uint32_t W = 2 * k;
@@ -816,38 +785,37 @@ int Engine::enqueue_extend_dah(const uint8_t* d_ods, uint32_t k, uint32_t n, uin
             stop = m;
             break;
         }
-    int rc;
     const bool cu_split = rs_cus_ > 0 && !profiling_;
-    if (cu_split && (rc = make_cu_streams())) return rc;
+    if (cu_split) CDA_TRY(make_cu_streams());
     // RS chunks: on aux_stream_, or (CU split) chunk 0 on the whole chip (s)
     // and the rest on the RS CUs; hashing on s, or on the complement CUs
     hipStream_t rs_q = cu_split ? rs_cu_stream_ : aux_stream_;
     hipStream_t hq = cu_split ? hash_cu_stream_ : s;
     hipEvent_t start = sync_event(0);
     if (!start || !sync_event(n_chunks + 1)) return fail(CDA_ERR_DEVICE, "hipEventCreate failed");
-    if ((rc = dah_prepare(W, n, d_err, s))) return rc;
+    CDA_TRY(dah_prepare(W, n, d_err, s));
     if (cu_split) {
-        if ((rc = enqueue_extend(d_ods, k, c, d_eds, s))) return rc;
-        if ((rc = check(hipEventRecord(sync_event(1), s), "hipEventRecord"))) return rc;
+        CDA_TRY(enqueue_extend(d_ods, k, c, d_eds, s));
+        CDA_TRY(check(hipEventRecord(sync_event(1), s), "hipEventRecord"));
     }
-    if ((rc = check(hipEventRecord(start, s), "hipEventRecord"))) return rc;
-    if ((rc = check(hipStreamWaitEvent(rs_q, start, 0), "hipStreamWaitEvent"))) return rc;
+    CDA_TRY(check(hipEventRecord(start, s), "hipEventRecord"));
+    CDA_TRY(check(hipStreamWaitEvent(rs_q, start, 0), "hipStreamWaitEvent"));
     for (uint32_t i = cu_split ? 1 : 0; i < n_chunks; i++) {
         const uint32_t i0 = i * c, m = (i0 + c <= n) ? c : n - i0;
-        if ((rc = enqueue_extend(d_ods ? d_ods + i0 * ods_sq : nullptr, k, m, d_eds + i0 * eds_sq, rs_q)))
-            return rc;   // rs_q is joined by the caller's drain (guarded_on)
+        // rs_q is joined by the caller's drain (guarded_on)
+        CDA_TRY(enqueue_extend(d_ods ? d_ods + i0 * ods_sq : nullptr, k, m, d_eds + i0 * eds_sq, rs_q));
         if (fault_at("extend_chunk"))
             return fail(CDA_ERR_DEVICE, "enqueue_extend_dah: injected fault after a chunk's RS (CDA_FAULT=extend_chunk)");
         hipEvent_t ev = sync_event(1 + i);
-        if ((rc = check(hipEventRecord(ev, rs_q), "hipEventRecord"))) return rc;
+        CDA_TRY(check(hipEventRecord(ev, rs_q), "hipEventRecord"));
     }
     Forest f[2], post[2];
     dah_forests(W, d_rows, d_cols, f);
     for (uint32_t i = 0; i < n_chunks; i++) {
         const uint32_t i0 = i * c, m = (i0 + c <= n) ? c : n - i0;
-        if ((rc = check(hipStreamWaitEvent(hq, sync_event(1 + i), 0), "hipStreamWaitEvent"))) return rc;
+        CDA_TRY(check(hipStreamWaitEvent(hq, sync_event(1 + i), 0), "hipStreamWaitEvent"));
         Forest p[2];
-        if ((rc = dah_chunk(d_eds, k, i0, m, stop, d_err, f, p, hq))) return rc;
+        CDA_TRY(dah_chunk(d_eds, k, i0, m, stop, d_err, f, p, hq));
         if (i == 0) {
             post[0] = p[0];
             post[1] = p[1];
@@ -855,8 +823,8 @@ int Engine::enqueue_extend_dah(const uint8_t* d_ods, uint32_t k, uint32_t n, uin
     }
     if (cu_split) {   // the latency-bound rest on the whole chip, in order on s
         hipEvent_t done = sync_event(n_chunks + 1);
-        if ((rc = check(hipEventRecord(done, hq), "hipEventRecord"))) return rc;
-        if ((rc = check(hipStreamWaitEvent(s, done, 0), "hipStreamWaitEvent"))) return rc;
+        CDA_TRY(check(hipEventRecord(done, hq), "hipEventRecord"));
+        CDA_TRY(check(hipStreamWaitEvent(s, done, 0), "hipStreamWaitEvent"));
     }
     return dah_finish(k, 0, n, stop, post, d_roots, d_err, d_status, s);
 }
@@ -870,7 +838,7 @@ int Engine::enqueue_rs(const uint8_t* d_data, uint8_t* d_parity, uint32_t k, uin
     }
     if (k == 0) return fail(CDA_ERR_UNSUPPORTED, "no shards");
     if (k > 1024) return fail(CDA_ERR_UNSUPPORTED, "more than 2048 shards");
-    if (!pow2(k)) {
+    if (!is_pow2(k)) {
         // klauspost leopardFF8/16 encode with dataShards = parityShards = k:
         // m = ceilPow2(k); the IFFT reads k data shards and zeros up to m
         // (ifftDITEncoder's mtrunc), the FFT's first k outputs are the parity.
@@ -878,15 +846,12 @@ int Engine::enqueue_rs(const uint8_t* d_data, uint8_t* d_parity, uint32_t k, uin
         uint32_t m = 1;
         while (m < k) m <<= 1;
         const size_t in_cw = (size_t)k * len, pad_cw = (size_t)m * len;
-        int rc;
-        if ((rc = check(rs_pad_.ensure(2 * pad_cw * n), "hipMalloc rs padding"))) return rc;
+        CDA_TRY(ensure(rs_pad_, 2 * pad_cw * n, "hipMalloc rs padding"));
         uint8_t* pad_in = rs_pad_.as<uint8_t>();
         uint8_t* pad_out = pad_in + pad_cw * n;
-        if ((rc = check(hipMemsetAsync(pad_in, 0, pad_cw * n, s), "hipMemsetAsync"))) return rc;
-        if ((rc = check(hipMemcpy2DAsync(pad_in, pad_cw, d_data, in_cw, in_cw, n, hipMemcpyDeviceToDevice, s),
-                        "copy")))
-            return rc;
-        if ((rc = enqueue_rs(pad_in, pad_out, m, len, n, s))) return rc;
+        CDA_TRY(fill(pad_in, 0, pad_cw * n, s, "hipMemsetAsync"));
+        CDA_TRY(check(hipMemcpy2DAsync(pad_in, pad_cw, d_data, in_cw, in_cw, n, hipMemcpyDeviceToDevice, s), "copy"));
+        CDA_TRY(enqueue_rs(pad_in, pad_out, m, len, n, s));
         return check(hipMemcpy2DAsync(d_parity, in_cw, pad_out, pad_cw, in_cw, n, hipMemcpyDeviceToDevice, s), "copy");
     }
     if (k == 1)
@@ -899,48 +864,55 @@ int Engine::enqueue_rs(const uint8_t* d_data, uint8_t* d_parity, uint32_t k, uin
 // last device batch, once that batch's GPU work (the call's end event) is done.
 int Engine::device_push_order_detail(uint32_t sq, int32_t* axis, uint32_t* index, uint32_t* pos) {
     if (sq >= dev_err_n_) return fail(CDA_ERR_INVALID, "square index beyond the last device batch");
-    int rc;
-    if (order_used_ && order_ev_ && (rc = check(hipEventSynchronize(order_ev_), "hipEventSynchronize (last call)")))
-        return rc;
-    uint32_t w = 0xFFFFFFFFu;
-    if ((rc = check(hipMemcpyAsync(&w, dev_err_.as<uint32_t>() + sq, 4, hipMemcpyDeviceToHost, stream_),
-                    "hipMemcpyAsync push-order word")))
-        return rc;
-    if ((rc = check(hipStreamSynchronize(stream_), "hipStreamSynchronize"))) return rc;
-    if (w == 0xFFFFFFFFu) {
-        *axis = -1;
-        *index = *pos = 0;
-    } else {
-        *axis = (int32_t)(w >> 24);
-        *index = (w >> 12) & 0xFFF;
-        *pos = w & 0xFFF;
-    }
+    if (order_used_ && order_ev_) CDA_TRY(check(hipEventSynchronize(order_ev_), "hipEventSynchronize (last call)"));
+    uint32_t w = push_order::kOrdered;
+    CDA_TRY(d2h(&w, dev_err_.as<uint32_t>() + sq, 4, stream_, "hipMemcpyAsync push-order word"));
+    CDA_TRY(sync(stream_));
+    const push_order::Violation v = push_order::decode(w);
+    *axis = v.axis;
+    *index = v.index;
+    *pos = v.pos;
     return CDA_OK;
+}
+
+int Engine::read_push_order(const void* d_words, uint32_t n, uint32_t* words, hipStream_t s) {
+    CDA_TRY(d2h(words, d_words, (size_t)n * 4, s, "D2H"));
+    return sync(s);
+}
+
+static_assert(push_order::kStatusOk == CDA_OK && push_order::kStatusViolation == CDA_ERR_PUSH_ORDER,
+              "push_order.h fill_status writes the C ABI's codes");
+
+int Engine::fail_push_order(const uint8_t* last_ns, const uint8_t* pushed_ns) {
+    auto ns_hex = [](const uint8_t* ns) {
+        std::string h;
+        char hx[3];
+        for (int i = 0; i < kNs; i++) {
+            snprintf(hx, sizeof hx, "%02x", ns ? ns[i] : 0xFF);
+            h += hx;
+        }
+        return h;
+    };
+    return fail(CDA_ERR_PUSH_ORDER, "pushed data has to be lexicographically ordered by namespace IDs: last namespace: " +
+                                        ns_hex(last_ns) + ", pushed: " + ns_hex(pushed_ns));
 }
 
 // Build the reference's error text for the first violating square.
 int Engine::push_order_error(const uint32_t* err_words, uint32_t n, const uint8_t* src, uint32_t k,
                              bool src_is_eds) {
     for (uint32_t sq = 0; sq < n; sq++) {
-        const uint32_t e = err_words[sq];
-        if (e == 0xFFFFFFFFu) continue;
-        po_axis = (int32_t)(e >> 24);
-        po_index = (e >> 12) & 0xFFF;
-        po_pos = e & 0xFFF;
+        const push_order::Violation v = push_order::decode(err_words[sq]);
+        if (v.axis < 0) continue;
+        po_axis = v.axis;
+        po_index = v.index;
+        po_pos = v.pos;
         const uint32_t w = src_is_eds ? 2 * k : k;
         const uint8_t* base = src + (size_t)sq * w * w * kShare;
         auto cell = [&](uint32_t pos) {
-            const uint32_t r = po_axis == 0 ? po_index : pos, c = po_axis == 0 ? pos : po_index;
+            const uint32_t r = v.axis == 0 ? v.index : pos, c = v.axis == 0 ? pos : v.index;
             return base + ((size_t)r * w + c) * kShare;
         };
-        std::string msg = "pushed data has to be lexicographically ordered by namespace IDs: last namespace: ";
-        char hx[3];
-        const uint8_t* last = cell(po_pos - 1);
-        const uint8_t* pushed = cell(po_pos);
-        for (int i = 0; i < kNs; i++) { snprintf(hx, sizeof hx, "%02x", last[i]); msg += hx; }
-        msg += ", pushed: ";
-        for (int i = 0; i < kNs; i++) { snprintf(hx, sizeof hx, "%02x", pushed[i]); msg += hx; }
-        return fail(CDA_ERR_PUSH_ORDER, msg);
+        return fail_push_order(cell(v.pos - 1), cell(v.pos));
     }
     return CDA_OK;
 }
@@ -1031,7 +1003,6 @@ __global__ __launch_bounds__(256) void pack_parity_kernel(const uint8_t* __restr
 int Engine::enqueue_parity_d2h(const uint8_t* d_eds, uint32_t k, uint32_t n, uint8_t* eds, hipStream_t from,
                                hipEvent_t ready, hipEvent_t done, int eds_mode, uint8_t* d_par) {
     const size_t W = 2 * (size_t)k, sq_b = W * W * kShare, half = k * W * kShare;
-    int rc;
     const size_t par_b = (size_t)n * 3 * k * k * kShare;
     if (eds_mode == CDA_EDS_PARITY) {
         // pack on the compute stream right behind the RS (a few hundred us per
@@ -1040,30 +1011,25 @@ int Engine::enqueue_parity_d2h(const uint8_t* d_eds, uint32_t k, uint32_t n, uin
         const uint64_t total16 = par_b / 16;
         hipLaunchKernelGGL(pack_parity_kernel, dim3((uint32_t)((total16 + 255) / 256)), dim3(256), 0, from, d_eds,
                            d_par, k, total16);
-        if ((rc = check(hipGetLastError(), "pack parity"))) return rc;
+        CDA_TRY(launched("pack parity"));
     }
-    if ((rc = check(hipEventRecord(ready, from), "hipEventRecord"))) return rc;
-    if ((rc = check(hipStreamWaitEvent(copy_out_, ready, 0), "hipStreamWaitEvent"))) return rc;
+    CDA_TRY(check(hipEventRecord(ready, from), "hipEventRecord"));
+    CDA_TRY(check(hipStreamWaitEvent(copy_out_, ready, 0), "hipStreamWaitEvent"));
     if (eds_mode == CDA_EDS_PARITY) {
-        if ((rc = check(hipMemcpyAsync(eds, d_par, par_b, hipMemcpyDeviceToHost, copy_out_), "D2H parity"))) return rc;
+        CDA_TRY(d2h(eds, d_par, par_b, copy_out_, "D2H parity"));
         return check(hipEventRecord(done, copy_out_), "hipEventRecord");
     }
     if (host_full_d2h_ && eds_mode == CDA_EDS_FULL) {   // the whole EDS back as one contiguous copy (Q0 included)
-        if ((rc = check(hipMemcpyAsync(eds, d_eds, n * sq_b, hipMemcpyDeviceToHost, copy_out_), "D2H EDS"))) return rc;
+        CDA_TRY(d2h(eds, d_eds, n * sq_b, copy_out_, "D2H EDS"));
         return check(hipEventRecord(done, copy_out_), "hipEventRecord");
     }
     // Q1 (rows 0..k-1, columns k..2k-1: strided) as 2-D copies, Q2|Q3 (rows
     // k..2k-1) linear (a second stream for the Q1 copies measured no faster:
     // profiles/r04/host_d2h_streams.txt)
     for (uint32_t sq = 0; sq < n; sq++) {
-        if ((rc = check(hipMemcpy2DAsync(eds + sq * sq_b + k * kShare, W * kShare, d_eds + sq * sq_b + k * kShare,
-                                         W * kShare, (size_t)k * kShare, k, hipMemcpyDeviceToHost, copy_out_),
-                        "D2H Q1")))
-            return rc;
-        if ((rc = check(hipMemcpyAsync(eds + sq * sq_b + half, d_eds + sq * sq_b + half, half, hipMemcpyDeviceToHost,
-                                       copy_out_),
-                        "D2H Q2|Q3")))
-            return rc;
+        CDA_TRY(check(hipMemcpy2DAsync(eds + sq * sq_b + k * kShare, W * kShare, d_eds + sq * sq_b + k * kShare,
+                W * kShare, (size_t)k * kShare, k, hipMemcpyDeviceToHost, copy_out_), "D2H Q1"));
+        CDA_TRY(d2h(eds + sq * sq_b + half, d_eds + sq * sq_b + half, half, copy_out_, "D2H Q2|Q3"));
     }
     return check(hipEventRecord(done, copy_out_), "hipEventRecord");
 }
@@ -1086,18 +1052,11 @@ int Engine::host_pipeline(const uint8_t* ods, uint32_t k, uint32_t n, uint8_t* e
     const size_t ods_sq = (size_t)k * k * kShare, eds_sq = (size_t)W * W * kShare, root_sq = (size_t)W * kNode;
     const bool packed = eds && eds_mode == CDA_EDS_PARITY;
     const size_t out_sq = packed ? 3 * ods_sq : eds_sq;   // bytes per square of the caller's eds buffer
-    int rc;
-    if ((rc = check(h_ods_.ensure(kPipeSlots * c * ods_sq), "hipMalloc"))) return rc;
-    if ((rc = check(h_eds_.ensure(kPipeSlots * c * eds_sq), "hipMalloc"))) return rc;
-    if (packed && (rc = check(h_par_.ensure(kPipeSlots * c * 3 * ods_sq), "hipMalloc"))) return rc;
-    if ((rc = check(h_rows_.ensure(n * root_sq), "hipMalloc"))) return rc;
-    if ((rc = check(h_cols_.ensure(n * root_sq), "hipMalloc"))) return rc;
-    if ((rc = check(h_roots_.ensure((size_t)n * 32), "hipMalloc"))) return rc;
-    if ((rc = check(err_buf_.ensure((size_t)n * 4), "hipMalloc"))) return rc;
+    CDA_TRY(host_stage(k, n, kPipeSlots * c, true, packed));
     hipStream_t s = stream_;
     // the buffers' allocation (stream-ordered on s) precedes the copies
-    if ((rc = check(hipEventRecord(pipe_comp_[0], s), "hipEventRecord"))) return rc;
-    if ((rc = check(hipStreamWaitEvent(copy_in_, pipe_comp_[0], 0), "hipStreamWaitEvent"))) return rc;
+    CDA_TRY(check(hipEventRecord(pipe_comp_[0], s), "hipEventRecord"));
+    CDA_TRY(check(hipStreamWaitEvent(copy_in_, pipe_comp_[0], 0), "hipStreamWaitEvent"));
     HostPin pin_ods(host_register_, ods, (size_t)n * ods_sq, copy_in_, s),
         pin_eds(host_register_, eds, (size_t)n * out_sq, s, copy_out_);
     uint32_t* err = err_buf_.as<uint32_t>();
@@ -1105,38 +1064,53 @@ int Engine::host_pipeline(const uint8_t* ods, uint32_t k, uint32_t n, uint8_t* e
         const uint32_t m = std::min(c, n - i0), slot = i % kPipeSlots;
         uint8_t* d_ods = h_ods_.as<uint8_t>() + slot * c * ods_sq;
         uint8_t* d_eds = h_eds_.as<uint8_t>() + slot * c * eds_sq;
-        if (i >= kPipeSlots && (rc = check(hipStreamWaitEvent(copy_in_, pipe_comp_[slot], 0), "hipStreamWaitEvent")))
-            return rc;
-        if ((rc = check(hipMemcpyAsync(d_ods, ods + i0 * ods_sq, m * ods_sq, hipMemcpyHostToDevice, copy_in_), "H2D")))
-            return rc;
-        if ((rc = check(hipEventRecord(pipe_in_[slot], copy_in_), "hipEventRecord"))) return rc;
-        if ((rc = check(hipStreamWaitEvent(s, pipe_in_[slot], 0), "hipStreamWaitEvent"))) return rc;
-        if (eds && i >= kPipeSlots && (rc = check(hipStreamWaitEvent(s, pipe_d2h_[slot], 0), "hipStreamWaitEvent")))
-            return rc;
-        if ((rc = enqueue_extend(d_ods, k, m, d_eds, s, err + i0))) return rc;
-        if (eds && (rc = enqueue_parity_d2h(d_eds, k, m, eds + i0 * out_sq, s, pipe_rs_[slot], pipe_d2h_[slot],
-                                            eds_mode, packed ? h_par_.as<uint8_t>() + slot * c * 3 * ods_sq : nullptr)))
-            return rc;
-        if ((rc = enqueue_dah(d_eds, k, m, h_rows_.as<uint8_t>() + i0 * root_sq, h_cols_.as<uint8_t>() + i0 * root_sq,
-                              h_roots_.as<uint8_t>() + (size_t)i0 * 32, err + i0, nullptr, s, true)))
-            return rc;
-        if ((rc = check(hipEventRecord(pipe_comp_[slot], s), "hipEventRecord"))) return rc;
+        if (i >= kPipeSlots) CDA_TRY(check(hipStreamWaitEvent(copy_in_, pipe_comp_[slot], 0), "hipStreamWaitEvent"));
+        CDA_TRY(h2d(d_ods, ods + i0 * ods_sq, m * ods_sq, copy_in_, "H2D"));
+        CDA_TRY(check(hipEventRecord(pipe_in_[slot], copy_in_), "hipEventRecord"));
+        CDA_TRY(check(hipStreamWaitEvent(s, pipe_in_[slot], 0), "hipStreamWaitEvent"));
+        if (eds && i >= kPipeSlots) CDA_TRY(check(hipStreamWaitEvent(s, pipe_d2h_[slot], 0), "hipStreamWaitEvent"));
+        CDA_TRY(enqueue_extend(d_ods, k, m, d_eds, s, err + i0));
+        if (eds) CDA_TRY(enqueue_parity_d2h(d_eds, k, m, eds + i0 * out_sq, s, pipe_rs_[slot], pipe_d2h_[slot],
+                         eds_mode, packed ? h_par_.as<uint8_t>() + slot * c * 3 * ods_sq : nullptr));
+        CDA_TRY(enqueue_dah(d_eds, k, m, h_rows_.as<uint8_t>() + i0 * root_sq, h_cols_.as<uint8_t>() + i0 * root_sq,
+                h_roots_.as<uint8_t>() + (size_t)i0 * 32, err + i0, nullptr, s, true));
+        CDA_TRY(check(hipEventRecord(pipe_comp_[slot], s), "hipEventRecord"));
         // (an error return leaves copies queued on copy_in_ / copy_out_: the
         // caller's drain (guarded_on) waits for them before the call returns)
         if (i == 1 && fault_at("pipe_chunk"))
             return fail(CDA_ERR_DEVICE, "host_pipeline: injected fault after chunk 1 (CDA_FAULT=pipe_chunk)");
     }
-    if ((rc = check(hipMemcpyAsync(rows, h_rows_.ptr, n * root_sq, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(cols, h_cols_.ptr, n * root_sq, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(roots, h_roots_.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
+    const bool host_q0 = eds && eds_mode == CDA_EDS_FULL && !host_full_d2h_;
+    return host_finish(ods, false, k, n, host_q0 ? eds : nullptr, rows, cols, roots, status,
+                       [&] { return eds ? sync(copy_out_) : CDA_OK; });
+}
+
+int Engine::host_stage(uint32_t k, uint32_t n, uint32_t resident, bool ods, bool packed) {
+    const size_t ods_b = (size_t)resident * k * k * kShare, roots_b = (size_t)n * 2 * k * kNode;
+    if (ods) CDA_TRY(ensure(h_ods_, ods_b, "hipMalloc"));
+    CDA_TRY(ensure(h_eds_, 4 * ods_b, "hipMalloc"));
+    CDA_TRY(ensure(h_rows_, roots_b, "hipMalloc"));
+    CDA_TRY(ensure(h_cols_, roots_b, "hipMalloc"));
+    CDA_TRY(ensure(h_roots_, (size_t)n * 32, "hipMalloc"));
+    CDA_TRY(ensure(err_buf_, (size_t)n * 4, "hipMalloc"));
+    if (packed) CDA_TRY(ensure(h_par_, 3 * ods_b, "hipMalloc"));
+    return CDA_OK;
+}
+
+int Engine::host_finish(const uint8_t* src, bool src_is_eds, uint32_t k, uint32_t n, uint8_t* q0_eds, uint8_t* rows,
+                        uint8_t* cols, uint8_t* roots, int32_t* status, const std::function<int()>& parity_wait) {
+    const size_t roots_b = (size_t)n * 2 * k * kNode;
+    hipStream_t s = stream_;
+    CDA_TRY(d2h(rows, h_rows_.ptr, roots_b, s, "D2H"));
+    CDA_TRY(d2h(cols, h_cols_.ptr, roots_b, s, "D2H"));
+    CDA_TRY(d2h(roots, h_roots_.ptr, (size_t)n * 32, s, "D2H"));
     std::vector<uint32_t> words(n);
-    if ((rc = check(hipMemcpyAsync(words.data(), err, (size_t)n * 4, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if (eds && eds_mode == CDA_EDS_FULL && !host_full_d2h_) copy_q0(ods, k, n, eds);   // host work while the GPU runs
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
-    if (eds && (rc = check(hipStreamSynchronize(copy_out_), "hipStreamSynchronize"))) return rc;
-    if (status)
-        for (uint32_t i = 0; i < n; i++) status[i] = words[i] == 0xFFFFFFFFu ? CDA_OK : CDA_ERR_PUSH_ORDER;
-    return push_order_error(words.data(), n, ods, k, false);
+    CDA_TRY(d2h(words.data(), err_buf_.ptr, (size_t)n * 4, s, "D2H"));
+    if (q0_eds) copy_q0(src, k, n, q0_eds);   // host work while the GPU runs
+    CDA_TRY(sync(s));
+    if (parity_wait) CDA_TRY(parity_wait());
+    push_order::fill_status(words.data(), n, status);
+    return push_order_error(words.data(), n, src, k, src_is_eds);
 }
 
 int Engine::host_extend_dah(const uint8_t* ods, uint32_t k, uint32_t n, uint8_t* eds, uint8_t* rows, uint8_t* cols,
@@ -1145,21 +1119,13 @@ int Engine::host_extend_dah(const uint8_t* ods, uint32_t k, uint32_t n, uint8_t*
         return fail(CDA_ERR_INVALID, "unknown eds_mode");
     const uint32_t W = 2 * k;
     const size_t ods_b = (size_t)n * k * k * kShare, eds_b = (size_t)n * W * W * kShare;
-    const size_t roots_b = (size_t)n * W * kNode;
     const bool packed = eds && eds_mode == CDA_EDS_PARITY;
     {   // big batches: the chunk pipeline (chunk ~ 256 MiB of ODS: 32 squares at k = 128)
         const size_t ods_sq = (size_t)k * k * kShare;
         const uint32_t c = host_pipe_chunk_ ? host_pipe_chunk_ : (uint32_t)std::max<size_t>(1, (256u << 20) / ods_sq);
         if (n > 2 * c) return host_pipeline(ods, k, n, eds, rows, cols, roots, status, c, eds_mode);
     }
-    int rc;
-    if ((rc = check(h_ods_.ensure(ods_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_eds_.ensure(eds_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_rows_.ensure(roots_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_cols_.ensure(roots_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_roots_.ensure((size_t)n * 32), "hipMalloc"))) return rc;
-    if ((rc = check(err_buf_.ensure((size_t)n * 4), "hipMalloc"))) return rc;
-    if (packed && (rc = check(h_par_.ensure(3 * ods_b), "hipMalloc"))) return rc;
+    CDA_TRY(host_stage(k, n, n, true, packed));
     hipStream_t s = stream_;
     HostPin pin_ods(host_register_, ods, ods_b, stream_, copy_out_),
         pin_eds(host_register_, eds, packed ? 3 * ods_b : eds_b, stream_, copy_out_);
@@ -1171,85 +1137,57 @@ int Engine::host_extend_dah(const uint8_t* ods, uint32_t k, uint32_t n, uint8_t*
     const uint32_t c = eds && host_chunk_ && n > host_chunk_ ? host_chunk_ : n;
     for (uint32_t i0 = 0; i0 < n; i0 += c) {
         const uint32_t m = std::min(c, n - i0);
-        if ((rc = check(hipMemcpyAsync(h_ods_.as<uint8_t>() + i0 * ods_sq, ods + i0 * ods_sq, m * ods_sq,
-                                       hipMemcpyHostToDevice, s),
-                        "H2D")))
-            return rc;
-        if ((rc = enqueue_extend(h_ods_.as<uint8_t>() + i0 * ods_sq, k, m, h_eds_.as<uint8_t>() + i0 * eds_sq, s,
-                                 err_buf_.as<uint32_t>() + i0)))
-            return rc;
-        if (eds && (rc = enqueue_parity_d2h(h_eds_.as<uint8_t>() + i0 * eds_sq, k, m,
-                                            eds + i0 * (packed ? 3 * ods_sq : eds_sq), s, ev_rs_, ev_out_, eds_mode,
-                                            packed ? h_par_.as<uint8_t>() + i0 * 3 * ods_sq : nullptr)))
-            return rc;
+        CDA_TRY(h2d(h_ods_.as<uint8_t>() + i0 * ods_sq, ods + i0 * ods_sq, m * ods_sq, s, "H2D"));
+        CDA_TRY(enqueue_extend(h_ods_.as<uint8_t>() + i0 * ods_sq, k, m, h_eds_.as<uint8_t>() + i0 * eds_sq, s,
+                err_buf_.as<uint32_t>() + i0));
+        if (eds) CDA_TRY(enqueue_parity_d2h(h_eds_.as<uint8_t>() + i0 * eds_sq, k, m,
+                         eds + i0 * (packed ? 3 * ods_sq : eds_sq), s, ev_rs_, ev_out_, eds_mode,
+                         packed ? h_par_.as<uint8_t>() + i0 * 3 * ods_sq : nullptr));
     }
-    if ((rc = enqueue_dah(h_eds_.as<uint8_t>(), k, n, h_rows_.as<uint8_t>(), h_cols_.as<uint8_t>(),
-                          h_roots_.as<uint8_t>(), err_buf_.as<uint32_t>(), nullptr, s, true)))
-        return rc;
-    if ((rc = check(hipMemcpyAsync(rows, h_rows_.ptr, roots_b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(cols, h_cols_.ptr, roots_b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(roots, h_roots_.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    std::vector<uint32_t> err(n);
-    if ((rc = check(hipMemcpyAsync(err.data(), err_buf_.ptr, (size_t)n * 4, hipMemcpyDeviceToHost, s), "D2H")))
-        return rc;
-    if (eds && eds_mode == CDA_EDS_FULL && !host_full_d2h_) copy_q0(ods, k, n, eds);   // host work while the GPU runs
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
-    if (eds && (rc = check(hipEventSynchronize(ev_out_), "hipEventSynchronize"))) return rc;
-    if (status)
-        for (uint32_t i = 0; i < n; i++) status[i] = err[i] == 0xFFFFFFFFu ? CDA_OK : CDA_ERR_PUSH_ORDER;
-    return push_order_error(err.data(), n, ods, k, false);
+    CDA_TRY(enqueue_dah(h_eds_.as<uint8_t>(), k, n, h_rows_.as<uint8_t>(), h_cols_.as<uint8_t>(),
+            h_roots_.as<uint8_t>(), err_buf_.as<uint32_t>(), nullptr, s, true));
+    const bool host_q0 = eds && eds_mode == CDA_EDS_FULL && !host_full_d2h_;
+    return host_finish(ods, false, k, n, host_q0 ? eds : nullptr, rows, cols, roots, status, [&] {
+        return eds ? check(hipEventSynchronize(ev_out_), "hipEventSynchronize") : CDA_OK;
+    });
 }
 
 int Engine::host_extend(const uint8_t* ods, uint32_t k, uint8_t* eds) {
     const uint32_t W = 2 * k;
     const size_t ods_b = (size_t)k * k * kShare, eds_b = (size_t)W * W * kShare;
-    int rc;
-    if ((rc = check(h_ods_.ensure(ods_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_eds_.ensure(eds_b), "hipMalloc"))) return rc;
+    CDA_TRY(ensure(h_ods_, ods_b, "hipMalloc"));
+    CDA_TRY(ensure(h_eds_, eds_b, "hipMalloc"));
     hipStream_t s = stream_;
     HostPin pin_ods(host_register_, ods, ods_b, stream_, copy_out_),
         pin_eds(host_register_, eds, eds_b, stream_, copy_out_);
-    if ((rc = check(hipMemcpyAsync(h_ods_.ptr, ods, ods_b, hipMemcpyHostToDevice, s), "H2D"))) return rc;
-    if ((rc = enqueue_extend(h_ods_.as<uint8_t>(), k, 1, h_eds_.as<uint8_t>(), s))) return rc;
-    if ((rc = enqueue_parity_d2h(h_eds_.as<uint8_t>(), k, 1, eds, s, ev_rs_, ev_out_))) return rc;
+    CDA_TRY(h2d(h_ods_.ptr, ods, ods_b, s, "H2D"));
+    CDA_TRY(enqueue_extend(h_ods_.as<uint8_t>(), k, 1, h_eds_.as<uint8_t>(), s));
+    CDA_TRY(enqueue_parity_d2h(h_eds_.as<uint8_t>(), k, 1, eds, s, ev_rs_, ev_out_));
     copy_q0(ods, k, 1, eds);
     return check(hipEventSynchronize(ev_out_), "hipEventSynchronize");
 }
 
 int Engine::host_dah(const uint8_t* eds, uint32_t k, uint8_t* rows, uint8_t* cols, uint8_t* root) {
     const uint32_t W = 2 * k;
-    const size_t eds_b = (size_t)W * W * kShare, roots_b = (size_t)W * kNode;
-    int rc;
-    if ((rc = check(h_eds_.ensure(eds_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_rows_.ensure(roots_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_cols_.ensure(roots_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_roots_.ensure(32), "hipMalloc"))) return rc;
-    if ((rc = check(err_buf_.ensure(4), "hipMalloc"))) return rc;
+    const size_t eds_b = (size_t)W * W * kShare;
+    CDA_TRY(host_stage(k, 1, 1, false, false));
     hipStream_t s = stream_;
     HostPin pin_eds(host_register_, eds, eds_b, stream_, copy_out_);
-    if ((rc = check(hipMemcpyAsync(h_eds_.ptr, eds, eds_b, hipMemcpyHostToDevice, s), "H2D"))) return rc;
-    if ((rc = enqueue_dah(h_eds_.as<uint8_t>(), k, 1, h_rows_.as<uint8_t>(), h_cols_.as<uint8_t>(),
-                          h_roots_.as<uint8_t>(), err_buf_.as<uint32_t>(), nullptr, s)))
-        return rc;
-    uint32_t err = 0;
-    if ((rc = check(hipMemcpyAsync(rows, h_rows_.ptr, roots_b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(cols, h_cols_.ptr, roots_b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(root, h_roots_.ptr, 32, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(&err, err_buf_.ptr, 4, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
-    return push_order_error(&err, 1, eds, k, true);
+    CDA_TRY(h2d(h_eds_.ptr, eds, eds_b, s, "H2D"));
+    CDA_TRY(enqueue_dah(h_eds_.as<uint8_t>(), k, 1, h_rows_.as<uint8_t>(), h_cols_.as<uint8_t>(),
+            h_roots_.as<uint8_t>(), err_buf_.as<uint32_t>(), nullptr, s));
+    return host_finish(eds, true, k, 1, nullptr, rows, cols, root, nullptr, nullptr);
 }
 
 int Engine::host_rs(const uint8_t* data, uint32_t k, uint32_t len, uint32_t n, uint8_t* parity) {
     const size_t b = (size_t)n * k * len;
-    int rc;
-    if ((rc = check(h_ods_.ensure(b), "hipMalloc"))) return rc;
-    if ((rc = check(h_eds_.ensure(b), "hipMalloc"))) return rc;
+    CDA_TRY(ensure(h_ods_, b, "hipMalloc"));
+    CDA_TRY(ensure(h_eds_, b, "hipMalloc"));
     hipStream_t s = stream_;
-    if ((rc = check(hipMemcpyAsync(h_ods_.ptr, data, b, hipMemcpyHostToDevice, s), "H2D"))) return rc;
-    if ((rc = enqueue_rs(h_ods_.as<uint8_t>(), h_eds_.as<uint8_t>(), k, len, n, s))) return rc;
-    if ((rc = check(hipMemcpyAsync(parity, h_eds_.ptr, b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    CDA_TRY(h2d(h_ods_.ptr, data, b, s, "H2D"));
+    CDA_TRY(enqueue_rs(h_ods_.as<uint8_t>(), h_eds_.as<uint8_t>(), k, len, n, s));
+    CDA_TRY(d2h(parity, h_eds_.ptr, b, s, "D2H"));
+    return sync(s);
 }
 
 int Engine::host_data_root(const uint8_t* rows, const uint8_t* cols, uint32_t w, uint8_t* root) {
@@ -1260,16 +1198,13 @@ int Engine::host_data_root(const uint8_t* rows, const uint8_t* cols, uint32_t w,
         memcpy(&slots[(size_t)i * kSlot], rows + (size_t)i * kNode, kNode);
         memcpy(&slots[(size_t)(w + i) * kSlot], cols + (size_t)i * kNode, kNode);
     }
-    int rc;
-    if ((rc = check(root_slots_.ensure(slots.size()), "hipMalloc"))) return rc;
-    if ((rc = check(h_roots_.ensure(32), "hipMalloc"))) return rc;
+    CDA_TRY(ensure(root_slots_, slots.size(), "hipMalloc"));
+    CDA_TRY(ensure(h_roots_, 32, "hipMalloc"));
     hipStream_t s = stream_;
-    if ((rc = check(hipMemcpyAsync(root_slots_.ptr, slots.data(), slots.size(), hipMemcpyHostToDevice, s), "H2D")))
-        return rc;
-    if ((rc = check(launch_data_root(root_slots_.as<uint8_t>(), 2 * w, 1, h_roots_.as<uint8_t>(), s), "data root")))
-        return rc;
-    if ((rc = check(hipMemcpyAsync(root, h_roots_.ptr, 32, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    CDA_TRY(h2d(root_slots_.ptr, slots.data(), slots.size(), s, "H2D"));
+    CDA_TRY(check(launch_data_root(root_slots_.as<uint8_t>(), 2 * w, 1, h_roots_.as<uint8_t>(), s), "data root"));
+    CDA_TRY(d2h(root, h_roots_.ptr, 32, s, "D2H"));
+    return sync(s);
 }
 
 }  // namespace cda

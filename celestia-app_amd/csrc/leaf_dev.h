@@ -57,16 +57,16 @@ __device__ __forceinline__ void leaf_order_check(const CellGrid& g, const uint8_
                                                  uint32_t gr, uint32_t gc) {
     const uint32_t k = g.k;
     uint32_t nb[8];
-    uint32_t key = 0xFFFFFFFFu;
+    uint32_t key = push_order::kOrdered;
     if (check_rows && gc + 1 < k && c + 1 < g.cols) {
         load_ns_be(cellp + kShare, nb);
-        if (ns_less(nb, nsw)) key = min(key, (0u << 24) | (gr << 12) | (gc + 1));
+        if (ns_less(nb, nsw)) key = min(key, push_order::encode(0, gr, gc + 1));
     }
     if (check_cols && gr + 1 < k && r + 1 < g.rows) {
         load_ns_be(cellp + (size_t)g.row_stride * kShare, nb);
-        if (ns_less(nb, nsw)) key = min(key, (1u << 24) | (gc << 12) | (gr + 1));
+        if (ns_less(nb, nsw)) key = min(key, push_order::encode(1, gc, gr + 1));
     }
-    if (key != 0xFFFFFFFFu) atomicMin(err, key);
+    if (key != push_order::kOrdered) atomicMin(err, key);
 }
 
 // The leaf node of cell (r, c) of square sq of grid g, stored to its 96-B

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(256) void row_order_kernel(const CellGrid g, uint32
     uint32_t me[8], nb[8];
     load_ns_be(E + ((size_t)r * g.row_stride + c) * SH, me);
     load_ns_be(E + ((size_t)r * g.row_stride + c + 1) * SH, nb);
-    if (ns_less(nb, me)) atomicMin(err + blockIdx.y, (0u << 24) | (gr << 12) | (gc + 1));
+    if (ns_less(nb, me)) atomicMin(err + blockIdx.y, push_order::encode(0, gr, gc + 1));
 }
 
 // One virtual block (bx = 256-cell group, by = square) of the leaf launch:

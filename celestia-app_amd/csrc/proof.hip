@@ -88,29 +88,28 @@ uint64_t ResidentSquare::col_level_offset(uint32_t L) const {   // bytes into `c
 }
 
 int Engine::square_create(const uint8_t* ods, uint32_t k, ResidentSquare* sq) {
-    if (!is_pow2(k) || k > 1024) return fail(CDA_ERR_INVALID, "square width must be a power of two <= 1024");
+    CDA_TRY(check_width(k));
     const uint32_t W = 2 * k, logW = ceil_log2(W);
     sq->k = k;
     sq->log_w = logW;
     const size_t ods_b = (size_t)k * k * kShare, eds_b = (size_t)W * W * kShare;
     hipStream_t s = stream_;
-    int rc;
-    if ((rc = check(sq->eds.ensure(eds_b), "hipMalloc"))) return rc;
-    if ((rc = check(sq->levels.ensure(sq->level_offset(logW + 1)), "hipMalloc"))) return rc;
-    if ((rc = check(sq->col_levels.ensure(sq->col_level_offset(logW + 1)), "hipMalloc"))) return rc;
-    if ((rc = check(sq->roots_slots.ensure((size_t)2 * W * kSlot), "hipMalloc"))) return rc;
-    if ((rc = check(sq->rfc.ensure((size_t)2 * (2 * W) * 32), "hipMalloc"))) return rc;
-    if ((rc = check(sq->rows.ensure((size_t)W * kNode), "hipMalloc"))) return rc;
-    if ((rc = check(sq->cols.ensure((size_t)W * kNode), "hipMalloc"))) return rc;
-    if ((rc = check(sq->root.ensure(32), "hipMalloc"))) return rc;
-    if ((rc = check(sq->err.ensure(4), "hipMalloc"))) return rc;
-    if ((rc = check(h_ods_.ensure(ods_b), "hipMalloc"))) return rc;
-    if ((rc = check(hipMemcpyAsync(h_ods_.ptr, ods, ods_b, hipMemcpyHostToDevice, s), "H2D"))) return rc;
-    if ((rc = enqueue_extend(h_ods_.as<uint8_t>(), k, 1, sq->eds.as<uint8_t>(), s))) return rc;
-    if ((rc = check(hipMemsetAsync(sq->err.ptr, 0xFF, 4, s), "hipMemsetAsync"))) return rc;
+    CDA_TRY(ensure(sq->eds, eds_b, "hipMalloc"));
+    CDA_TRY(ensure(sq->levels, sq->level_offset(logW + 1), "hipMalloc"));
+    CDA_TRY(ensure(sq->col_levels, sq->col_level_offset(logW + 1), "hipMalloc"));
+    CDA_TRY(ensure(sq->roots_slots, (size_t)2 * W * kSlot, "hipMalloc"));
+    CDA_TRY(ensure(sq->rfc, (size_t)2 * (2 * W) * 32, "hipMalloc"));
+    CDA_TRY(ensure(sq->rows, (size_t)W * kNode, "hipMalloc"));
+    CDA_TRY(ensure(sq->cols, (size_t)W * kNode, "hipMalloc"));
+    CDA_TRY(ensure(sq->root, 32, "hipMalloc"));
+    CDA_TRY(ensure(sq->err, 4, "hipMalloc"));
+    CDA_TRY(ensure(h_ods_, ods_b, "hipMalloc"));
+    CDA_TRY(h2d(h_ods_.ptr, ods, ods_b, s, "H2D"));
+    CDA_TRY(enqueue_extend(h_ods_.as<uint8_t>(), k, 1, sq->eds.as<uint8_t>(), s));
+    CDA_TRY(fill(sq->err.ptr, 0xFF, 4, s, "hipMemsetAsync"));
     uint8_t* lv = sq->levels.as<uint8_t>();
     const CellGrid g{sq->eds.as<uint8_t>(), 0, W, W, W, 0, 0, k};
-    if ((rc = check(launch_leaves(g, 1, lv, sq->err.as<uint32_t>(), true, true, s), "leaf hashing"))) return rc;
+    CDA_TRY(check(launch_leaves(g, 1, lv, sq->err.as<uint32_t>(), true, true, s), "leaf hashing"));
     // both forests: every level retained (the columns' for the column-axis sample proofs, sample.hip)
     Forest f[2]{};
     f[0] = Forest{lv, 0, W, W, 1, nullptr, 0, sq->rows.as<uint8_t>(), 0, sq->roots_slots.as<uint8_t>(), 0, 0};
@@ -119,7 +118,7 @@ int Engine::square_create(const uint8_t* ods, uint32_t k, ResidentSquare* sq) {
     for (uint32_t m = W; m >= 2; m /= 2, L++) {
         f[0].out = lv + sq->level_offset(L);
         f[1].out = sq->col_levels.as<uint8_t>() + sq->col_level_offset(L);
-        if ((rc = check(launch_level(f, 2, m, 1, s), "nmt level"))) return rc;
+        CDA_TRY(check(launch_level(f, 2, m, 1, s), "nmt level"));
         for (int i = 0; i < 2; i++) {
             f[i].in = f[i].out;
             f[i].tree_stride = m / 2;
@@ -127,17 +126,12 @@ int Engine::square_create(const uint8_t* ods, uint32_t k, ResidentSquare* sq) {
         }
     }
     // data root with every RFC-6962 level kept: leaf digests, then one workgroup
-    if ((rc = check(launch_rfc_leaves(sq->roots_slots.as<uint8_t>(), 2 * W, sq->rfc.as<uint32_t>(), s), "rfc leaves")))
-        return rc;
+    CDA_TRY(check(launch_rfc_leaves(sq->roots_slots.as<uint8_t>(), 2 * W, sq->rfc.as<uint32_t>(), s), "rfc leaves"));
     hipLaunchKernelGGL(rfc_levels_kernel, dim3(1), dim3(1024), 0, s, sq->rfc.as<uint32_t>(), 2 * W,
                        sq->root.as<uint8_t>());
-    if ((rc = check(hipGetLastError(), "rfc levels"))) return rc;
-    uint32_t e = 0;
-    if ((rc = check(hipMemcpyAsync(&e, sq->err.ptr, 4, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
-    sq->push_err = e;
-    if (e != 0xFFFFFFFFu) return push_order_error(&e, 1, ods, k, false);
-    return CDA_OK;
+    CDA_TRY(launched("rfc levels"));
+    CDA_TRY(read_push_order(sq->err.ptr, 1, &sq->push_err, s));
+    return push_order_error(&sq->push_err, 1, ods, k, false);
 }
 
 int Engine::square_read(ResidentSquare* sq, ResidentSquare::Part part, uint8_t* out) {
@@ -147,23 +141,20 @@ int Engine::square_read(ResidentSquare* sq, ResidentSquare::Part part, uint8_t* 
                       : part == ResidentSquare::kDataRoot ? &sq->root
                                                           : &sq->eds;
     const size_t len = part == ResidentSquare::kDataRoot ? 32 : part == ResidentSquare::kEds ? W * W * kShare : W * kNode;
-    int rc;
-    if ((rc = check(hipMemcpyAsync(out, b->ptr, len, hipMemcpyDeviceToHost, stream_), "D2H"))) return rc;
-    return check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    CDA_TRY(d2h(out, b->ptr, len, stream_, "D2H"));
+    return sync(stream_);
 }
 
 int Engine::square_gather(ResidentSquare* sq, const std::vector<GatherPiece>& pieces, uint8_t* out, size_t out_len) {
-    int rc;
-    if ((rc = square_gather_device(sq, pieces, out_len))) return rc;
+    CDA_TRY(square_gather_device(sq, pieces, out_len));
     hipStream_t s = stream_;
-    if ((rc = check(hipMemcpyAsync(out, sq->scratch.ptr, out_len, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    CDA_TRY(d2h(out, sq->scratch.ptr, out_len, s, "D2H"));
+    return sync(s);
 }
 
 int Engine::square_gather_device(ResidentSquare* sq, const std::vector<GatherPiece>& pieces, size_t out_len) {
     hipStream_t s = stream_;
-    int rc;
-    if ((rc = check(sq->scratch.ensure(out_len ? out_len : 1), "hipMalloc"))) return rc;
+    CDA_TRY(ensure(sq->scratch, out_len ? out_len : 1, "hipMalloc"));
     if (pieces.empty()) return CDA_OK;
     std::vector<Piece> P(pieces.size());
     for (size_t i = 0; i < pieces.size(); i++) {
@@ -175,15 +166,13 @@ int Engine::square_gather_device(ResidentSquare* sq, const std::vector<GatherPie
                                                           : &sq->roots_slots;
         P[i] = Piece{b->as<uint8_t>() + g.src, g.dst, g.len, g.buf == GatherPiece::kRfc ? 1u : 0u};
     }
-    if ((rc = check(sq->pieces.ensure(P.size() * sizeof(Piece)), "hipMalloc"))) return rc;
-    if ((rc = check(hipMemcpyAsync(sq->pieces.ptr, P.data(), P.size() * sizeof(Piece), hipMemcpyHostToDevice, s),
-                    "H2D pieces")))
-        return rc;
+    CDA_TRY(ensure(sq->pieces, P.size() * sizeof(Piece), "hipMalloc"));
+    CDA_TRY(h2d(sq->pieces.ptr, P.data(), P.size() * sizeof(Piece), s, "H2D pieces"));
     hipLaunchKernelGGL(gather_kernel, dim3((uint32_t)P.size()), dim3(256), 0, s, sq->pieces.as<Piece>(),
                        sq->scratch.as<uint8_t>());
-    if ((rc = check(hipGetLastError(), "gather"))) return rc;
+    CDA_TRY(launched("gather"));
     // `P` is pageable: make sure the copy has left it before returning
-    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    return sync(s);
 }
 
 // ---------------------------------------------------------------------------
@@ -229,8 +218,7 @@ int Engine::square_share_proof(ResidentSquare* sq, uint32_t start, uint32_t end,
                                          au_off + ((size_t)i * naunts + l) * 32, 32});
     }
     std::vector<uint8_t> buf(total);
-    int rc;
-    if ((rc = square_gather(sq, pieces, buf.data(), total))) return rc;
+    CDA_TRY(square_gather(sq, pieces, buf.data(), total));
     o->start_row = startRow;
     o->end_row = endRow;
     if (o->shares) std::memcpy(o->shares, buf.data(), sh_b);
@@ -262,8 +250,7 @@ int Engine::square_subtree_root(ResidentSquare* sq, uint32_t row, const uint8_t*
                                   ? GatherPiece{GatherPiece::kRows, (uint64_t)row * kNode, 0, kNode}
                                   : GatherPiece{GatherPiece::kLevels,
                                                 sq->level_offset(L) + ((uint64_t)row * (W >> L) + pos) * kSlot, 0, kNode};
-    int rc;
-    if ((rc = square_gather(sq, {piece}, out, kNode))) return rc;
+    CDA_TRY(square_gather(sq, {piece}, out, kNode));
     if (walk_len > logW) {   // walk(leaf, rest): the leaf is not in the cache -- Go's %v of its bytes
         std::string msg = "did not find sub tree root: [";
         for (uint32_t i = 0; i < kNode; i++) msg += (i ? " " : "") + std::to_string(out[i]);
@@ -354,19 +341,16 @@ int Engine::square_blob_commitments(ResidentSquare* sq, const uint32_t* starts, 
         max_n = std::max(max_n, cnt);
     }
     const uint32_t n_slots = bt.back();
-    int rc;
-    if ((rc = square_gather_device(sq, pieces, (size_t)n_slots * kSlot))) return rc;
+    CDA_TRY(square_gather_device(sq, pieces, (size_t)n_slots * kSlot));
     hipStream_t s = stream_;
-    if ((rc = check(cm_roots_.ensure((size_t)n_slots * 32 + 32), "hipMalloc"))) return rc;
-    if ((rc = check(cm_plan_.ensure(bt.size() * 4), "hipMalloc"))) return rc;
-    if ((rc = check(cm_out_.ensure((size_t)n * 32), "hipMalloc"))) return rc;
-    if ((rc = check(hipMemcpyAsync(cm_plan_.ptr, bt.data(), bt.size() * 4, hipMemcpyHostToDevice, s), "H2D"))) return rc;
-    if ((rc = check(launch_slot_merkle_roots(sq->scratch.as<uint8_t>(), cm_plan_.as<uint32_t>(), n, n_slots, max_n,
-                                             cm_roots_.as<uint32_t>(), cm_out_.as<uint8_t>(), s),
-                    "commitment roots")))
-        return rc;
-    if ((rc = check(hipMemcpyAsync(out, cm_out_.ptr, (size_t)n * 32, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    CDA_TRY(ensure(cm_roots_, (size_t)n_slots * 32 + 32, "hipMalloc"));
+    CDA_TRY(ensure(cm_plan_, bt.size() * 4, "hipMalloc"));
+    CDA_TRY(ensure(cm_out_, (size_t)n * 32, "hipMalloc"));
+    CDA_TRY(h2d(cm_plan_.ptr, bt.data(), bt.size() * 4, s, "H2D"));
+    CDA_TRY(check(launch_slot_merkle_roots(sq->scratch.as<uint8_t>(), cm_plan_.as<uint32_t>(), n, n_slots, max_n,
+            cm_roots_.as<uint32_t>(), cm_out_.as<uint8_t>(), s), "commitment roots"));
+    CDA_TRY(d2h(out, cm_out_.ptr, (size_t)n * 32, s, "D2H"));
+    return sync(s);
 }
 
 }  // namespace cda

@@ -293,12 +293,11 @@ int Engine::ensure_gf8_tables() {
     if (gf8_log_.ptr) return CDA_OK;
     auto F = std::make_unique<LeoField<8>>();
     leo_build<8>(*F, 0x11D, kCantor8);
-    int rc;
     for (auto [buf, src, len] : {std::tuple{&gf8_log_, (const void*)F->log, sizeof F->log},
                                  std::tuple{&gf8_exp_, (const void*)F->exp, sizeof F->exp},
                                  std::tuple{&gf8_skew_, (const void*)F->skew, sizeof F->skew}}) {
-        if ((rc = check(buf->ensure_fixed(len), "hipMalloc"))) return rc;   // filled by a host copy below
-        if ((rc = check(hipMemcpy(buf->ptr, src, len, hipMemcpyHostToDevice), "hipMemcpy"))) return rc;
+        CDA_TRY(check(buf->ensure_fixed(len), "hipMalloc"));   // filled by a host copy below
+        CDA_TRY(check(hipMemcpy(buf->ptr, src, len, hipMemcpyHostToDevice), "hipMemcpy"));
     }
     return CDA_OK;
 }
@@ -309,7 +308,7 @@ int Engine::ensure_gf8_tables() {
 uint8_t* Engine::rp_stage(const void* src, size_t n, hipStream_t s, int* rc) {
     const size_t need = (n + 63) & ~(size_t)63;
     if (rp_host_used_ + need > rp_host_bytes_) {
-        if ((*rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return nullptr;
+        if ((*rc = sync(s))) return nullptr;
         rp_host_used_ = 0;
         if (need > rp_host_bytes_) {
             if (rp_host_) (void)hipHostFree(rp_host_);
@@ -335,20 +334,19 @@ int Engine::decode_codewords(uint8_t* d_eds, uint8_t* d_present, uint32_t k, uin
     int rc;
     FieldDev F;
     if (k <= 128) {
-        if ((rc = ensure_gf8_tables())) return rc;
+        CDA_TRY(ensure_gf8_tables());
         F = FieldDev{gf8_log_.as<uint16_t>(), gf8_exp_.as<uint16_t>(), gf8_skew_.as<uint16_t>(), 8, 255};
     } else {
         F = FieldDev{gf16_log_.as<uint16_t>(), gf16_exp_.as<uint16_t>(), gf16_skew_.as<uint16_t>(), 16, 65535};
     }
-    if ((rc = check(rp_cw_.ensure((size_t)n_cw * sizeof(Cw)), "hipMalloc"))) return rc;
-    if ((rc = check(rp_err_.ensure((size_t)n_cw * n * 2), "hipMalloc"))) return rc;
+    CDA_TRY(ensure(rp_cw_, (size_t)n_cw * sizeof(Cw), "hipMalloc"));
+    CDA_TRY(ensure(rp_err_, (size_t)n_cw * n * 2, "hipMalloc"));
     const uint8_t* staged = rp_stage(axis_index.data(), (size_t)n_cw * sizeof(Cw), s, &rc);
     if (!staged) return rc;
-    if ((rc = check(hipMemcpyAsync(rp_cw_.ptr, staged, (size_t)n_cw * sizeof(Cw), hipMemcpyHostToDevice, s), "H2D")))
-        return rc;
+    CDA_TRY(h2d(rp_cw_.ptr, staged, (size_t)n_cw * sizeof(Cw), s, "H2D"));
     hipLaunchKernelGGL(errloc_kernel, dim3(n_cw), dim3(256), n * 4, s, F, rp_cw_.as<Cw>(), d_present, k,
                        rp_err_.as<uint16_t>());
-    if ((rc = check(hipGetLastError(), "errloc"))) return rc;
+    CDA_TRY(launched("errloc"));
     const uint32_t S = k <= 128 ? 64 : 32;
     const size_t lds = (size_t)2 * n * S * 2;
     if (k <= 128) {
@@ -356,17 +354,14 @@ int Engine::decode_codewords(uint8_t* d_eds, uint8_t* d_present, uint32_t k, uin
         hipLaunchKernelGGL(decode8_kernel, dim3(n_cw * (shard_len / 64)), dim3(256), lds8, s, F.skew, rp_cw_.as<Cw>(),
                            d_eds, d_present, k, rp_err_.as<uint16_t>(), shard_len);
     } else {
-        if (lds > 64 * 1024 &&
-            (rc = check(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_kernel<16>),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-                        "hipFuncSetAttribute")))
-            return rc;
+        if (lds > 64 * 1024) CDA_TRY(check(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_kernel<16>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute"));
         hipLaunchKernelGGL(decode_kernel<16>, dim3(n_cw * (shard_len / 64)), dim3(256), lds, s, F, rp_cw_.as<Cw>(),
                            d_eds, d_present, k, rp_err_.as<uint16_t>(), shard_len);
     }
-    if ((rc = check(hipGetLastError(), "decode"))) return rc;
+    CDA_TRY(launched("decode"));
     hipLaunchKernelGGL(mark_kernel, dim3((n_cw * n + 255) / 256), dim3(256), 0, s, rp_cw_.as<Cw>(), n_cw, d_present, n);
-    return check(hipGetLastError(), "mark");
+    return launched("mark");
 }
 
 namespace {
@@ -393,23 +388,21 @@ int Engine::repair_verify(const uint8_t* E, uint32_t k, const uint8_t* row_roots
                           std::vector<uint8_t>& bad, hipStream_t s) {
     const uint32_t W = 2 * k, SH = kShare;
     const size_t roots_b = (size_t)W * kNode;
-    int rc;
-    if ((rc = check(rp_parity_.ensure((size_t)2 * W * k * SH), "hipMalloc"))) return rc;
-    if ((rc = check(rp_flags_.ensure((size_t)2 * W * 4), "hipMalloc"))) return rc;
-    if ((rc = enqueue_dah(E, k, 1, h_rows_.as<uint8_t>(), h_cols_.as<uint8_t>(), nullptr, err_buf_.as<uint32_t>(),
-                          nullptr, s)))
-        return rc;
+    CDA_TRY(ensure(rp_parity_, (size_t)2 * W * k * SH, "hipMalloc"));
+    CDA_TRY(ensure(rp_flags_, (size_t)2 * W * 4, "hipMalloc"));
+    CDA_TRY(enqueue_dah(E, k, 1, h_rows_.as<uint8_t>(), h_cols_.as<uint8_t>(), nullptr, err_buf_.as<uint32_t>(),
+            nullptr, s));
     RsJob j{};
     j.src = E;
     j.dst = rp_parity_.as<uint8_t>();
     j.n_seg = 2;
     j.seg[0] = RsSeg{W, 0, W * SH, SH, 0, k * SH, SH};              // rows: data half = cells 0..k-1
     j.seg[1] = RsSeg{W, 0, SH, W * SH, W * k * SH, k * SH, SH};     // columns
-    if ((rc = check(launch_rs(j, k, 1, gf16(k), s), "parity re-encode"))) return rc;
-    if ((rc = check(hipMemsetAsync(rp_flags_.ptr, 0, (size_t)2 * W * 4, s), "hipMemsetAsync"))) return rc;
+    CDA_TRY(check(launch_rs(j, k, 1, gf16(k), s), "parity re-encode"));
+    CDA_TRY(fill(rp_flags_.ptr, 0, (size_t)2 * W * 4, s, "hipMemsetAsync"));
     hipLaunchKernelGGL(parity_compare_kernel, dim3(2 * W, k), dim3(64), 0, s, E, rp_parity_.as<uint8_t>(), k,
                        rp_flags_.as<uint32_t>());
-    if ((rc = check(hipGetLastError(), "parity compare"))) return rc;
+    CDA_TRY(launched("parity compare"));
     // results land in pinned memory: the copies queue right behind the
     // kernels (a pageable destination makes each copy wait for the stream and
     // go through a staging blit)
@@ -418,15 +411,14 @@ int Engine::repair_verify(const uint8_t* E, uint32_t k, const uint8_t* row_roots
         if (rp_out_) (void)hipHostFree(rp_out_);
         rp_out_ = nullptr;
         rp_out_bytes_ = 0;
-        if ((rc = check(hipHostMalloc(&rp_out_, out_b, hipHostMallocDefault), "hipHostMalloc"))) return rc;
+        CDA_TRY(check(hipHostMalloc(&rp_out_, out_b, hipHostMallocDefault), "hipHostMalloc"));
         rp_out_bytes_ = out_b;
     }
     uint8_t* ob = static_cast<uint8_t*>(rp_out_);
-    if ((rc = check(hipMemcpyAsync(ob, h_rows_.ptr, roots_b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(ob + roots_b, h_cols_.ptr, roots_b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(ob + 2 * roots_b, rp_flags_.ptr, flags_b, hipMemcpyDeviceToHost, s), "D2H")))
-        return rc;
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
+    CDA_TRY(d2h(ob, h_rows_.ptr, roots_b, s, "D2H"));
+    CDA_TRY(d2h(ob + roots_b, h_cols_.ptr, roots_b, s, "D2H"));
+    CDA_TRY(d2h(ob + 2 * roots_b, rp_flags_.ptr, flags_b, s, "D2H"));
+    CDA_TRY(sync(s));
     const std::vector<uint8_t> rows(ob, ob + roots_b), cols(ob + roots_b, ob + 2 * roots_b);
     std::vector<uint32_t> flags(2 * W);
     std::memcpy(flags.data(), ob + 2 * roots_b, flags_b);
@@ -468,7 +460,7 @@ int Engine::host_repair(uint8_t* eds, const uint8_t* present_in, uint32_t W, con
 int Engine::device_repair(uint8_t* d_eds, const uint8_t* present_in, uint32_t W, const uint8_t* row_roots,
                           const uint8_t* col_roots, int32_t* byz_axis, uint32_t* byz_index) {
     // the square may have been written on any stream of the caller
-    if (int rc = check(hipDeviceSynchronize(), "hipDeviceSynchronize")) return rc;
+    CDA_TRY(check(hipDeviceSynchronize(), "hipDeviceSynchronize"));
     return repair(nullptr, d_eds, present_in, W, row_roots, col_roots, byz_axis, byz_index);
 }
 
@@ -481,35 +473,34 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
     if (W < 2 || (W & (W - 1)) || k > 512) return fail(CDA_ERR_INVALID, "EDS width must be a power of two in [2, 1024]");
     const size_t eds_b = (size_t)W * W * kShare, roots_b = (size_t)W * kNode;
     hipStream_t s = stream_;
-    int rc;
     // earlier copies out of the staging area are done once s is idle
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
+    CDA_TRY(sync(s));
     rp_host_used_ = 0;
     DevBuf& stage = d_eds ? rp_buf_ : h_eds_;
-    if ((rc = check(stage.ensure(eds_b), "hipMalloc"))) return rc;
-    if ((rc = check(rp_present_.ensure((size_t)W * W), "hipMalloc"))) return rc;
-    if ((rc = check(h_rows_.ensure(roots_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_cols_.ensure(roots_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_roots_.ensure(32), "hipMalloc"))) return rc;
-    if ((rc = check(err_buf_.ensure(4), "hipMalloc"))) return rc;
+    CDA_TRY(ensure(stage, eds_b, "hipMalloc"));
+    CDA_TRY(ensure(rp_present_, (size_t)W * W, "hipMalloc"));
+    CDA_TRY(ensure(h_rows_, roots_b, "hipMalloc"));
+    CDA_TRY(ensure(h_cols_, roots_b, "hipMalloc"));
+    CDA_TRY(ensure(h_roots_, 32, "hipMalloc"));
+    CDA_TRY(ensure(err_buf_, 4, "hipMalloc"));
     std::vector<uint8_t> present;
     uint8_t* E = d_eds ? d_eds : h_eds_.as<uint8_t>();
     bool first = true;
     auto upload = [&]() -> int {
         present.assign(present_in, present_in + (size_t)W * W);
         for (auto& v : present) v = v ? 1 : 0;
-        int r;
         if (!d_eds) {
-            if ((r = check(hipMemcpyAsync(E, eds, eds_b, hipMemcpyHostToDevice, s), "H2D"))) return r;
+            CDA_TRY(h2d(E, eds, eds_b, s, "H2D"));
         } else if (first) {
-            if ((r = check(hipMemcpyAsync(stage.ptr, E, eds_b, hipMemcpyDeviceToDevice, s), "D2D"))) return r;
-        } else if ((r = check(hipMemcpyAsync(E, stage.ptr, eds_b, hipMemcpyDeviceToDevice, s), "D2D"))) {
-            return r;
+            CDA_TRY(check(hipMemcpyAsync(stage.ptr, E, eds_b, hipMemcpyDeviceToDevice, s), "D2D"));
+        } else {
+            CDA_TRY(check(hipMemcpyAsync(E, stage.ptr, eds_b, hipMemcpyDeviceToDevice, s), "D2D"));
         }
         first = false;
+        int r;
         const uint8_t* staged = rp_stage(present.data(), present.size(), s, &r);
         if (!staged) return r;
-        return check(hipMemcpyAsync(rp_present_.ptr, staged, present.size(), hipMemcpyHostToDevice, s), "H2D");
+        return h2d(rp_present_.ptr, staged, present.size(), s, "H2D");
     };
     auto cell = [&](uint32_t axis, uint32_t i, uint32_t p) {
         return axis == 0 ? (size_t)i * W + p : (size_t)p * W + i;
@@ -520,9 +511,8 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
         return c;
     };
     auto download = [&](int code) -> int {
-        int r;
-        if (!d_eds && (r = check(hipMemcpyAsync(eds, E, eds_b, hipMemcpyDeviceToHost, s), "D2H"))) return r;
-        if ((r = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return r;
+        if (!d_eds) CDA_TRY(d2h(eds, E, eds_b, s, "D2H"));
+        CDA_TRY(sync(s));
         return code;
     };
     auto byzantine = [&](uint32_t axis, uint32_t i) {
@@ -543,8 +533,7 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
     // in the input keeps its cells through the sweeps, so a clean final
     // verification implies this check passed.
     auto precheck = [&]() -> int {
-        int r;
-        if ((r = repair_verify(E, k, row_roots, col_roots, bad, s))) return r;
+        CDA_TRY(repair_verify(E, k, row_roots, col_roots, bad, s));
         for (uint32_t i = 0; i < W; i++)
             for (uint32_t axis = 0; axis < 2; axis++) {
                 if (count(axis, i) != W) continue;
@@ -560,7 +549,7 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
             }
         return CDA_OK;
     };
-    if ((rc = upload())) return rc;
+    CDA_TRY(upload());
     // ---- fast path: batched sweeps to the fixed point, then verification
     bool solved = false;
     for (;;) {
@@ -572,7 +561,7 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
                 if (c != W && c >= k) cw.push_back(axis), cw.push_back(i);
             }
             if (cw.empty()) continue;
-            if ((rc = decode_codewords(E, rp_present_.as<uint8_t>(), k, kShare, cw, s))) return rc;
+            CDA_TRY(decode_codewords(E, rp_present_.as<uint8_t>(), k, kShare, cw, s));
             for (size_t q = 1; q < cw.size(); q += 2)
                 for (uint32_t p = 0; p < W; p++) present[cell(axis, cw[q], p)] = 1;
             progress = true;
@@ -580,7 +569,7 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
         solved = std::all_of(present.begin(), present.end(), [](uint8_t v) { return v != 0; });
         if (solved || !progress) break;
     }
-    if ((rc = repair_verify(E, k, row_roots, col_roots, bad, s))) return rc;
+    CDA_TRY(repair_verify(E, k, row_roots, col_roots, bad, s));
     bool clean = true;
     for (uint32_t axis = 0; axis < 2 && clean; axis++)
         for (uint32_t i = 0; i < W && clean; i++)
@@ -593,8 +582,8 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
     }
     // ---- error path: from the input again, the sanity check, then the exact
     // replay of solveCrossword
-    if ((rc = upload())) return rc;
-    if ((rc = precheck())) return rc;
+    CDA_TRY(upload());
+    CDA_TRY(precheck());
     for (;;) {
         bool all = true, progress = false;
         for (uint32_t i = 0; i < W; i++)
@@ -610,10 +599,10 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
                 for (uint32_t o = 0; o < W; o++)
                     was[o] = !present[cell(axis, i, o)] && count(ox, o) == W - 1;
                 const std::vector<uint32_t> cw{axis, i};
-                if ((rc = decode_codewords(E, rp_present_.as<uint8_t>(), k, kShare, cw, s))) return rc;
+                CDA_TRY(decode_codewords(E, rp_present_.as<uint8_t>(), k, kShare, cw, s));
                 for (uint32_t p = 0; p < W; p++) present[cell(axis, i, p)] = 1;
                 progress = true;
-                if ((rc = repair_verify(E, k, row_roots, col_roots, bad, s))) return rc;
+                CDA_TRY(repair_verify(E, k, row_roots, col_roots, bad, s));
                 // the rebuilt vector against its root, then the orthogonal
                 // vectors it completed against their roots and encodings
                 if (bad[axis * W + i] & 1) return byzantine(axis, i);
@@ -652,19 +641,16 @@ int Engine::host_rs_decode(uint8_t* shards, const uint8_t* present, uint32_t k, 
     }
     hipStream_t s = stream_;
     const size_t b = (size_t)n_codewords * W * shard_len;
-    int rc;
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
+    CDA_TRY(sync(s));
     rp_host_used_ = 0;
-    if ((rc = check(rp_buf_.ensure(b), "hipMalloc"))) return rc;
-    if ((rc = check(rp_present_.ensure((size_t)n_codewords * W), "hipMalloc"))) return rc;
-    if ((rc = check(hipMemcpyAsync(rp_buf_.ptr, shards, b, hipMemcpyHostToDevice, s), "H2D"))) return rc;
-    if ((rc = check(hipMemcpyAsync(rp_present_.ptr, present, (size_t)n_codewords * W, hipMemcpyHostToDevice, s),
-                    "H2D")))
-        return rc;
+    CDA_TRY(ensure(rp_buf_, b, "hipMalloc"));
+    CDA_TRY(ensure(rp_present_, (size_t)n_codewords * W, "hipMalloc"));
+    CDA_TRY(h2d(rp_buf_.ptr, shards, b, s, "H2D"));
+    CDA_TRY(h2d(rp_present_.ptr, present, (size_t)n_codewords * W, s, "H2D"));
     // row codewords of a "W-wide" grid: cell (i, p) = codeword i, shard p
-    if ((rc = decode_codewords(rp_buf_.as<uint8_t>(), rp_present_.as<uint8_t>(), k, shard_len, cw, s))) return rc;
-    if ((rc = check(hipMemcpyAsync(shards, rp_buf_.ptr, b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    CDA_TRY(decode_codewords(rp_buf_.as<uint8_t>(), rp_present_.as<uint8_t>(), k, shard_len, cw, s));
+    CDA_TRY(d2h(shards, rp_buf_.ptr, b, s, "D2H"));
+    return sync(s);
 }
 
 }  // namespace cda

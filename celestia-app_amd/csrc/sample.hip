@@ -205,11 +205,9 @@ int Engine::square_sample_proofs(ResidentSquare* sq, const uint32_t* rows, const
                  r_nd = region(o.nmt_nodes, (size_t)n * D * kNode), r_rt = region(o.axis_roots, (size_t)n * kNode),
                  r_lh = region(o.leaf_hash, (size_t)n * 32), r_au = region(o.aunts, (size_t)n * A * 32);
     hipStream_t s = stream_;
-    int rc;
-    if ((rc = check(sq->scratch.ensure(total), "hipMalloc"))) return rc;
+    CDA_TRY(ensure(sq->scratch, total, "hipMalloc"));
     uint8_t* scr = sq->scratch.as<uint8_t>();
-    if ((rc = check(hipMemcpyAsync(scr, packed.data(), (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D samples")))
-        return rc;
+    CDA_TRY(h2d(scr, packed.data(), (size_t)n * 4, s, "H2D samples"));
     auto dev = [&](const Region& r) -> uint8_t* { return r.host ? scr + r.off : nullptr; };
     SampleArgs a{};
     a.coords = reinterpret_cast<const uint32_t*>(scr);
@@ -228,13 +226,11 @@ int Engine::square_sample_proofs(ResidentSquare* sq, const uint32_t* rows, const
     a.leaf_hash = dev(r_lh);
     a.aunts = dev(r_au);
     hipLaunchKernelGGL(sample_kernel, dim3((n + kSampleWaves - 1) / kSampleWaves), dim3(64 * kSampleWaves), 0, s, a);
-    if ((rc = check(hipGetLastError(), "sample proofs"))) return rc;
+    CDA_TRY(launched("sample proofs"));
     for (const Region* r : {&r_sh, &r_ns, &r_nd, &r_rt, &r_lh, &r_au})
-        if (r->bytes &&
-            (rc = check(hipMemcpyAsync(r->host, scr + r->off, r->bytes, hipMemcpyDeviceToHost, s), "D2H samples")))
-            return rc;
+        if (r->bytes) CDA_TRY(d2h(r->host, scr + r->off, r->bytes, s, "D2H samples"));
     // `packed` is pageable and the outputs are the caller's: complete before returning
-    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    return sync(s);
 }
 
 int Engine::sample_proofs_verify(uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,

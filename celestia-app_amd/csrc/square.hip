@@ -117,24 +117,22 @@ hipError_t launch_share_writer(const Segment* segs, uint32_t n_segs, const uint3
 int Engine::enqueue_square(const square::Plan& p, const uint8_t* d_txs, uint8_t* d_ods, hipStream_t s) {
     const size_t seg_b = p.segs.size() * sizeof(Segment);
     const size_t plan_b = seg_b + p.compact.size();
-    int rc;
     // The plan goes through an engine-owned pinned buffer so the copy stays
     // asynchronous; the previous call's copy must have left it first.
-    if (sq_event_ && (rc = check(hipEventSynchronize(sq_event_), "hipEventSynchronize"))) return rc;
+    if (sq_event_) CDA_TRY(check(hipEventSynchronize(sq_event_), "hipEventSynchronize"));
     if (plan_b > sq_stage_bytes_) {
         if (sq_stage_) (void)hipHostFree(sq_stage_);
         sq_stage_ = nullptr;
         sq_stage_bytes_ = 0;
-        if ((rc = check(hipHostMalloc(&sq_stage_, plan_b, hipHostMallocDefault), "hipHostMalloc"))) return rc;
+        CDA_TRY(check(hipHostMalloc(&sq_stage_, plan_b, hipHostMallocDefault), "hipHostMalloc"));
         sq_stage_bytes_ = plan_b;
     }
-    if (!sq_event_ && (rc = check(hipEventCreateWithFlags(&sq_event_, hipEventDisableTiming), "hipEventCreate")))
-        return rc;
+    if (!sq_event_) CDA_TRY(check(hipEventCreateWithFlags(&sq_event_, hipEventDisableTiming), "hipEventCreate"));
     std::memcpy(sq_stage_, p.segs.data(), seg_b);
     if (!p.compact.empty()) std::memcpy(static_cast<uint8_t*>(sq_stage_) + seg_b, p.compact.data(), p.compact.size());
-    if ((rc = check(sq_plan_.ensure(plan_b), "hipMalloc"))) return rc;
-    if ((rc = check(hipMemcpyAsync(sq_plan_.ptr, sq_stage_, plan_b, hipMemcpyHostToDevice, s), "H2D plan"))) return rc;
-    if ((rc = check(hipEventRecord(sq_event_, s), "hipEventRecord"))) return rc;
+    CDA_TRY(ensure(sq_plan_, plan_b, "hipMalloc"));
+    CDA_TRY(h2d(sq_plan_.ptr, sq_stage_, plan_b, s, "H2D plan"));
+    CDA_TRY(check(hipEventRecord(sq_event_, s), "hipEventRecord"));
     const uint32_t n_shares = p.square_size * p.square_size;
     return check(launch_share_writer(sq_plan_.as<Segment>(), (uint32_t)p.segs.size(), nullptr,
                                      sq_plan_.as<uint8_t>() + seg_b, d_txs, d_ods, n_shares, s),
@@ -142,23 +140,21 @@ int Engine::enqueue_square(const square::Plan& p, const uint8_t* d_txs, uint8_t*
 }
 
 int Engine::upload_txs(const uint8_t* txs, size_t len, hipStream_t s) {
-    int rc;
     // 16 bytes of slack: the writer's aligned dword loads may run past the
     // last blob byte (the loaded bytes are masked off).
-    if ((rc = check(sq_txs_.ensure(len + 16), "hipMalloc"))) return rc;
-    if (len && (rc = check(hipMemcpyAsync(sq_txs_.ptr, txs, len, hipMemcpyHostToDevice, s), "H2D txs"))) return rc;
+    CDA_TRY(ensure(sq_txs_, len + 16, "hipMalloc"));
+    if (len) CDA_TRY(h2d(sq_txs_.ptr, txs, len, s, "H2D txs"));
     return CDA_OK;
 }
 
 int Engine::host_square(const square::Plan& p, const uint8_t* txs, size_t txs_len, uint8_t* ods) {
     const size_t ods_b = (size_t)p.square_size * p.square_size * kShare;
     hipStream_t s = stream_;
-    int rc;
-    if ((rc = check(h_ods_.ensure(ods_b), "hipMalloc"))) return rc;
-    if ((rc = upload_txs(txs, txs_len, s))) return rc;
-    if ((rc = enqueue_square(p, sq_txs_.as<uint8_t>(), h_ods_.as<uint8_t>(), s))) return rc;
-    if ((rc = check(hipMemcpyAsync(ods, h_ods_.ptr, ods_b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    CDA_TRY(ensure(h_ods_, ods_b, "hipMalloc"));
+    CDA_TRY(upload_txs(txs, txs_len, s));
+    CDA_TRY(enqueue_square(p, sq_txs_.as<uint8_t>(), h_ods_.as<uint8_t>(), s));
+    CDA_TRY(d2h(ods, h_ods_.ptr, ods_b, s, "D2H"));
+    return sync(s);
 }
 
 int Engine::host_construct_extend_dah(const square::Plan& p, const uint8_t* txs, size_t txs_len, uint8_t* eds,
@@ -166,30 +162,22 @@ int Engine::host_construct_extend_dah(const square::Plan& p, const uint8_t* txs,
     const uint32_t k = p.square_size, W = 2 * k;
     const size_t ods_b = (size_t)k * k * kShare, eds_b = (size_t)W * W * kShare, roots_b = (size_t)W * kNode;
     hipStream_t s = stream_;
-    int rc;
-    if ((rc = check(h_ods_.ensure(ods_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_eds_.ensure(eds_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_rows_.ensure(roots_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_cols_.ensure(roots_b), "hipMalloc"))) return rc;
-    if ((rc = check(h_roots_.ensure(32), "hipMalloc"))) return rc;
-    if ((rc = check(err_buf_.ensure(4), "hipMalloc"))) return rc;
-    if ((rc = upload_txs(txs, txs_len, s))) return rc;
-    if ((rc = enqueue_square(p, sq_txs_.as<uint8_t>(), h_ods_.as<uint8_t>(), s))) return rc;
-    if ((rc = enqueue_extend_dah(h_ods_.as<uint8_t>(), k, 1, h_eds_.as<uint8_t>(), h_rows_.as<uint8_t>(),
-                                 h_cols_.as<uint8_t>(), h_roots_.as<uint8_t>(), err_buf_.as<uint32_t>(), nullptr, s)))
-        return rc;
-    if (eds && (rc = check(hipMemcpyAsync(eds, h_eds_.ptr, eds_b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(rows, h_rows_.ptr, roots_b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(cols, h_cols_.ptr, roots_b, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipMemcpyAsync(root, h_roots_.ptr, 32, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
+    CDA_TRY(host_stage(k, 1, 1, true, false));
+    CDA_TRY(upload_txs(txs, txs_len, s));
+    CDA_TRY(enqueue_square(p, sq_txs_.as<uint8_t>(), h_ods_.as<uint8_t>(), s));
+    CDA_TRY(enqueue_extend_dah(h_ods_.as<uint8_t>(), k, 1, h_eds_.as<uint8_t>(), h_rows_.as<uint8_t>(),
+            h_cols_.as<uint8_t>(), h_roots_.as<uint8_t>(), err_buf_.as<uint32_t>(), nullptr, s));
+    if (eds) CDA_TRY(d2h(eds, h_eds_.ptr, eds_b, s, "D2H"));
+    CDA_TRY(d2h(rows, h_rows_.ptr, roots_b, s, "D2H"));
+    CDA_TRY(d2h(cols, h_cols_.ptr, roots_b, s, "D2H"));
+    CDA_TRY(d2h(root, h_roots_.ptr, 32, s, "D2H"));
     uint32_t err = 0;
-    if ((rc = check(hipMemcpyAsync(&err, err_buf_.ptr, 4, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
-    if (err == 0xFFFFFFFFu) return CDA_OK;
+    CDA_TRY(read_push_order(err_buf_.ptr, 1, &err, s));
+    if (err == push_order::kOrdered) return CDA_OK;
     // A namespace out of order in Q0 (e.g. a blob in a reserved namespace):
     // fetch the ODS once to name the offending namespaces.
     std::vector<uint8_t> ods(ods_b);
-    if ((rc = check(hipMemcpy(ods.data(), h_ods_.ptr, ods_b, hipMemcpyDeviceToHost), "D2H"))) return rc;
+    CDA_TRY(check(hipMemcpy(ods.data(), h_ods_.ptr, ods_b, hipMemcpyDeviceToHost), "D2H"));
     return push_order_error(&err, 1, ods.data(), k, false);
 }
 

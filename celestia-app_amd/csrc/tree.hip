@@ -147,13 +147,6 @@ __global__ __launch_bounds__(96) void gen_pack_roots_kernel(const uint8_t* __res
         roots[(size_t)t * kNode + threadIdx.x] = top[t * tree_stride + threadIdx.x];
 }
 
-const uint8_t kEmptyRoot[kNode] = {
-    // NmtHasher.EmptyRoot: 0^29 || 0^29 || sha256("")
-    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-    0xe3, 0xb0, 0xc4, 0x42, 0x98, 0xfc, 0x1c, 0x14, 0x9a, 0xfb, 0xf4, 0xc8, 0x99, 0x6f, 0xb9, 0x24,
-    0x27, 0xae, 0x41, 0xe4, 0x64, 0x9b, 0x93, 0x4c, 0xa4, 0x95, 0x99, 0x1b, 0x78, 0x52, 0xb8, 0x55};
-
 }  // namespace
 
 // All levels of n_trees erasured trees over host cells into tr_ (device):
@@ -170,101 +163,89 @@ int Engine::build_trees(const uint8_t* cells, uint32_t cell_len, uint32_t n_cell
         total += (uint64_t)cnt[L] * n_trees * kSlot;
     }
     const uint64_t cells_b = (uint64_t)n_trees * n_cells * cell_len;
-    int rc;
-    if ((rc = check(tr_cells_.ensure(cells_b + 16), "hipMalloc tree cells"))) return rc;
-    if ((rc = check(tr_levels_.ensure(total), "hipMalloc tree levels"))) return rc;
-    if ((rc = check(tr_axis_.ensure((size_t)n_trees * 8), "hipMalloc tree axes"))) return rc;
+    CDA_TRY(ensure(tr_cells_, cells_b + 16, "hipMalloc tree cells"));
+    CDA_TRY(ensure(tr_levels_, total, "hipMalloc tree levels"));
+    CDA_TRY(ensure(tr_axis_, (size_t)n_trees * 8, "hipMalloc tree axes"));
     uint32_t* d_axis = tr_axis_.as<uint32_t>();
     uint32_t* d_err = d_axis + n_trees;
-    if ((rc = check(hipMemcpyAsync(tr_cells_.ptr, cells, cells_b, hipMemcpyHostToDevice, s), "H2D"))) return rc;
-    if ((rc = check(hipMemcpyAsync(d_axis, axis, (size_t)n_trees * 4, hipMemcpyHostToDevice, s), "H2D"))) return rc;
-    if ((rc = check(hipMemsetAsync(d_err, 0xFF, (size_t)n_trees * 4, s), "hipMemsetAsync"))) return rc;
+    CDA_TRY(h2d(tr_cells_.ptr, cells, cells_b, s, "H2D"));
+    CDA_TRY(h2d(d_axis, axis, (size_t)n_trees * 4, s, "H2D"));
+    CDA_TRY(fill(d_err, 0xFF, (size_t)n_trees * 4, s, "hipMemsetAsync"));
     uint8_t* lv = tr_levels_.as<uint8_t>();
     const uint64_t n_leaves = (uint64_t)n_trees * n_cells;
     hipLaunchKernelGGL(gen_leaf_kernel, dim3((uint32_t)((n_leaves + 255) / 256)), dim3(256), 0, s,
                        tr_cells_.as<uint8_t>(), cell_len, n_cells, n_trees, square_size, d_axis, lv, d_err);
-    if ((rc = check(hipGetLastError(), "tree leaves"))) return rc;
+    CDA_TRY(launched("tree leaves"));
     for (size_t L = 1; L < cnt.size(); L++) {
         const uint64_t work = (uint64_t)n_trees * cnt[L];
         hipLaunchKernelGGL(gen_level_kernel, dim3((uint32_t)((work + 255) / 256)), dim3(256), 0, s,
                            lv + (*level_off)[L - 1], cnt[L - 1], lv + (*level_off)[L], n_trees,
                            (uint64_t)cnt[L - 1] * kSlot, (uint64_t)cnt[L] * kSlot);
-        if ((rc = check(hipGetLastError(), "tree level"))) return rc;
+        CDA_TRY(launched("tree level"));
     }
     err_out->assign(n_trees, 0);
-    if ((rc = check(hipMemcpyAsync(err_out->data(), d_err, (size_t)n_trees * 4, hipMemcpyDeviceToHost, s), "D2H")))
-        return rc;
+    CDA_TRY(d2h(err_out->data(), d_err, (size_t)n_trees * 4, s, "D2H"));
     return CDA_OK;
 }
 
 int Engine::tree_order_error(const uint8_t* cells, uint32_t cell_len, uint32_t n_cells, uint32_t square_size,
                              const uint32_t* axis, const std::vector<uint32_t>& err, int32_t* status) {
-    int rc = CDA_OK;
+    // (these trees' words are the bare push position of the first violation, ~0 = ordered)
+    push_order::fill_status(err.data(), err.size(), status);
     for (size_t t = 0; t < err.size(); t++) {
-        if (status) status[t] = err[t] == 0xFFFFFFFFu ? CDA_OK : CDA_ERR_PUSH_ORDER;
-        if (err[t] == 0xFFFFFFFFu || rc != CDA_OK) continue;
+        if (err[t] == push_order::kOrdered) continue;
         const uint32_t i = err[t];
-        auto ns_hex = [&](uint32_t pos) {
-            const uint8_t* c = cells + ((uint64_t)t * n_cells + pos) * cell_len;
+        auto ns = [&](uint32_t pos) -> const uint8_t* {   // NULL: a parity cell
             const bool par = !(pos < square_size && axis[t] < square_size);
-            std::string h;
-            char hx[3];
-            for (int b = 0; b < kNs; b++) {
-                snprintf(hx, sizeof hx, "%02x", par ? 0xFF : c[b]);
-                h += hx;
-            }
-            return h;
+            return par ? nullptr : cells + ((uint64_t)t * n_cells + pos) * cell_len;
         };
         po_axis = 0;
         po_index = axis[t];
         po_pos = i;
-        rc = fail(CDA_ERR_PUSH_ORDER, "pushed data has to be lexicographically ordered by namespace IDs: last namespace: " +
-                                          ns_hex(i - 1) + ", pushed: " + ns_hex(i));
+        return fail_push_order(ns(i - 1), ns(i));
     }
-    return rc;
+    return CDA_OK;
 }
 
 int Engine::nmt_axis_roots(const uint8_t* cells, uint32_t cell_len, uint32_t n_cells, uint32_t n_trees,
                            uint32_t square_size, const uint32_t* axis, uint8_t* roots, int32_t* status) {
-    if (n_cells == 0) {   // no pushes: NmtHasher.EmptyRoot
+    if (n_cells == 0) {   // no pushes: NmtHasher.EmptyRoot = 0^29 || 0^29 || sha256("")
         for (uint32_t t = 0; t < n_trees; t++) {
-            memcpy(roots + (size_t)t * kNode, kEmptyRoot, kNode);
+            memset(roots + (size_t)t * kNode, 0, 2 * kNs);
+            memcpy(roots + (size_t)t * kNode + 2 * kNs, kSha256Empty, 32);
             if (status) status[t] = CDA_OK;
         }
         return CDA_OK;
     }
     hipStream_t s = stream_;
-    int rc;
     bool consecutive = true;
     for (uint32_t t = 1; t < n_trees; t++) consecutive = consecutive && axis[t] == axis[0] + t;
     if (cell_len == (uint32_t)kShare && n_cells >= 2 && is_pow2(n_cells) && consecutive && axis[0] + n_trees <= 4096 &&
         n_cells < 4096) {
         // square-shaped: the tuned leaf / level kernels of nmt.hip
         const uint64_t cells_b = (uint64_t)n_trees * n_cells * kShare, slots = (uint64_t)n_trees * n_cells * kSlot;
-        if ((rc = check(tr_cells_.ensure(cells_b), "hipMalloc tree cells"))) return rc;
-        if ((rc = check(tr_levels_.ensure(2 * slots), "hipMalloc tree levels"))) return rc;
-        if ((rc = check(tr_axis_.ensure((size_t)n_trees * kNode + 64), "hipMalloc tree roots"))) return rc;
+        CDA_TRY(ensure(tr_cells_, cells_b, "hipMalloc tree cells"));
+        CDA_TRY(ensure(tr_levels_, 2 * slots, "hipMalloc tree levels"));
+        CDA_TRY(ensure(tr_axis_, (size_t)n_trees * kNode + 64, "hipMalloc tree roots"));
         uint8_t* d_roots = tr_axis_.as<uint8_t>();
         uint32_t* d_err = reinterpret_cast<uint32_t*>(d_roots + (((size_t)n_trees * kNode + 15) & ~(size_t)15));
         uint8_t* leaf = tr_levels_.as<uint8_t>();
         uint8_t* lvl = leaf + slots;
-        if ((rc = check(hipMemcpyAsync(tr_cells_.ptr, cells, cells_b, hipMemcpyHostToDevice, s), "H2D"))) return rc;
-        if ((rc = check(hipMemsetAsync(d_err, 0xFF, 4, s), "hipMemsetAsync"))) return rc;
+        CDA_TRY(h2d(tr_cells_.ptr, cells, cells_b, s, "H2D"));
+        CDA_TRY(fill(d_err, 0xFF, 4, s, "hipMemsetAsync"));
         const CellGrid g{tr_cells_.as<uint8_t>(), 0, n_trees, n_cells, n_cells, axis[0], 0, square_size};
-        if ((rc = check(launch_leaves(g, 1, leaf, d_err, true, false, s), "leaf hashing"))) return rc;
+        CDA_TRY(check(launch_leaves(g, 1, leaf, d_err, true, false, s), "leaf hashing"));
         Forest f{leaf, 0, n_trees, n_cells, 1, nullptr, 0, d_roots, 0, nullptr, 0, 0};
         const uint64_t off0[1] = {0};
-        if ((rc = run_forests(&f, 1, n_cells, 1, lvl, leaf, 0, off0, s))) return rc;
+        CDA_TRY(run_forests(&f, 1, n_cells, 1, lvl, leaf, 0, off0, s));
         uint32_t err = 0;
-        if ((rc = check(hipMemcpyAsync(roots, d_roots, (size_t)n_trees * kNode, hipMemcpyDeviceToHost, s), "D2H")))
-            return rc;
-        if ((rc = check(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-        if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
+        CDA_TRY(d2h(roots, d_roots, (size_t)n_trees * kNode, s, "D2H"));
+        CDA_TRY(read_push_order(d_err, 1, &err, s));
         // err = min over the batch's violations: a single word cannot tell
         // which other trees broke push order, so a batch with any violation
         // is re-run on the generic kernels, which keep one word per tree
         // (rare: an honest square never gets here)
-        if (err == 0xFFFFFFFFu) {
+        if (err == push_order::kOrdered) {
             if (status)
                 for (uint32_t t = 0; t < n_trees; t++) status[t] = CDA_OK;
             return CDA_OK;
@@ -272,14 +253,13 @@ int Engine::nmt_axis_roots(const uint8_t* cells, uint32_t cell_len, uint32_t n_c
     }
     std::vector<uint64_t> off;
     std::vector<uint32_t> err;
-    if ((rc = build_trees(cells, cell_len, n_cells, n_trees, square_size, axis, &off, &err))) return rc;
-    if ((rc = check(tr_roots_.ensure((size_t)n_trees * kNode), "hipMalloc tree roots"))) return rc;
+    CDA_TRY(build_trees(cells, cell_len, n_cells, n_trees, square_size, axis, &off, &err));
+    CDA_TRY(ensure(tr_roots_, (size_t)n_trees * kNode, "hipMalloc tree roots"));
     hipLaunchKernelGGL(gen_pack_roots_kernel, dim3(n_trees), dim3(96), 0, s, tr_levels_.as<uint8_t>() + off.back(),
                        (uint64_t)kSlot, n_trees, tr_roots_.as<uint8_t>());
-    if ((rc = check(hipGetLastError(), "pack roots"))) return rc;
-    if ((rc = check(hipMemcpyAsync(roots, tr_roots_.ptr, (size_t)n_trees * kNode, hipMemcpyDeviceToHost, s), "D2H")))
-        return rc;
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
+    CDA_TRY(launched("pack roots"));
+    CDA_TRY(d2h(roots, tr_roots_.ptr, (size_t)n_trees * kNode, s, "D2H"));
+    CDA_TRY(sync(s));
     return tree_order_error(cells, cell_len, n_cells, square_size, axis, err, status);
 }
 
@@ -288,10 +268,9 @@ int Engine::nmt_prove_range(const uint8_t* cells, uint32_t cell_len, uint32_t n_
                             uint8_t* root) {
     if (start >= end || end > n_cells) return fail(CDA_ERR_INVALID, "invalid proof range");
     hipStream_t s = stream_;
-    int rc;
     std::vector<uint64_t> off;
     std::vector<uint32_t> err;
-    if ((rc = build_trees(cells, cell_len, n_cells, 1, square_size, &axis, &off, &err))) return rc;
+    CDA_TRY(build_trees(cells, cell_len, n_cells, 1, square_size, &axis, &off, &err));
     std::vector<std::pair<uint32_t, uint32_t>> ids;
     prove_nodes(0, n_cells, start, end, ids);
     const std::vector<uint32_t> cnt = level_counts(n_cells);
@@ -299,16 +278,16 @@ int Engine::nmt_prove_range(const uint8_t* cells, uint32_t cell_len, uint32_t n_
     for (size_t i = 0; i < ids.size(); i++) src[i] = off[ids[i].first] + (uint64_t)ids[i].second * kSlot;
     src[ids.size()] = off.back();   // the root
     const uint32_t n = (uint32_t)src.size();
-    if ((rc = check(tr_roots_.ensure((size_t)n * (kNode + 8) + 64), "hipMalloc proof nodes"))) return rc;
+    CDA_TRY(ensure(tr_roots_, (size_t)n * (kNode + 8) + 64, "hipMalloc proof nodes"));
     uint64_t* d_src = tr_roots_.as<uint64_t>();
     uint8_t* d_out = tr_roots_.as<uint8_t>() + (size_t)n * 8;
-    if ((rc = check(hipMemcpyAsync(d_src, src.data(), (size_t)n * 8, hipMemcpyHostToDevice, s), "H2D"))) return rc;
+    CDA_TRY(h2d(d_src, src.data(), (size_t)n * 8, s, "H2D"));
     hipLaunchKernelGGL(gen_gather_nodes_kernel, dim3(n), dim3(64), 0, s, tr_levels_.as<uint8_t>(), d_src, n, d_out);
-    if ((rc = check(hipGetLastError(), "gather nodes"))) return rc;
+    CDA_TRY(launched("gather nodes"));
     std::vector<uint8_t> host((size_t)n * kNode);
-    if ((rc = check(hipMemcpyAsync(host.data(), d_out, host.size(), hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
-    if ((rc = tree_order_error(cells, cell_len, n_cells, square_size, &axis, err, nullptr))) return rc;
+    CDA_TRY(d2h(host.data(), d_out, host.size(), s, "D2H"));
+    CDA_TRY(sync(s));
+    CDA_TRY(tree_order_error(cells, cell_len, n_cells, square_size, &axis, err, nullptr));
     if (nodes) memcpy(nodes, host.data(), (size_t)(n - 1) * kNode);
     if (n_nodes) *n_nodes = n - 1;
     if (root) memcpy(root, host.data() + (size_t)(n - 1) * kNode, kNode);
@@ -317,26 +296,23 @@ int Engine::nmt_prove_range(const uint8_t* cells, uint32_t cell_len, uint32_t n_
 
 int Engine::merkle_root(const uint8_t* items, const uint64_t* off, uint32_t n, uint8_t* out) {
     hipStream_t s = stream_;
-    int rc;
     const uint64_t bytes = off[n] - off[0];
     std::vector<uint64_t> rel(n + 1);
     for (uint32_t i = 0; i <= n; i++) rel[i] = off[i] - off[0];
-    if ((rc = check(tr_cells_.ensure(bytes + 16), "hipMalloc merkle items"))) return rc;
-    if ((rc = check(tr_levels_.ensure((size_t)n * 32), "hipMalloc merkle digests"))) return rc;
-    if ((rc = check(tr_axis_.ensure((size_t)(n + 1) * 8 + 64), "hipMalloc merkle offsets"))) return rc;
+    CDA_TRY(ensure(tr_cells_, bytes + 16, "hipMalloc merkle items"));
+    CDA_TRY(ensure(tr_levels_, (size_t)n * 32, "hipMalloc merkle digests"));
+    CDA_TRY(ensure(tr_axis_, (size_t)(n + 1) * 8 + 64, "hipMalloc merkle offsets"));
     uint64_t* d_off = tr_axis_.as<uint64_t>();
     uint8_t* d_root = reinterpret_cast<uint8_t*>(d_off + n + 1);
-    if (bytes && (rc = check(hipMemcpyAsync(tr_cells_.ptr, items + off[0], bytes, hipMemcpyHostToDevice, s), "H2D")))
-        return rc;
-    if ((rc = check(hipMemcpyAsync(d_off, rel.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, s), "H2D")))
-        return rc;
+    if (bytes) CDA_TRY(h2d(tr_cells_.ptr, items + off[0], bytes, s, "H2D"));
+    CDA_TRY(h2d(d_off, rel.data(), (size_t)(n + 1) * 8, s, "H2D"));
     hipLaunchKernelGGL(gen_rfc_leaf_kernel, dim3((n + 255) / 256), dim3(256), 0, s, tr_cells_.as<uint8_t>(), d_off, n,
                        tr_levels_.as<uint32_t>());
-    if ((rc = check(hipGetLastError(), "merkle leaves"))) return rc;
+    CDA_TRY(launched("merkle leaves"));
     hipLaunchKernelGGL(gen_rfc_levels_kernel, dim3(1), dim3(256), 0, s, tr_levels_.as<uint32_t>(), n, d_root);
-    if ((rc = check(hipGetLastError(), "merkle levels"))) return rc;
-    if ((rc = check(hipMemcpyAsync(out, d_root, 32, hipMemcpyDeviceToHost, s), "D2H"))) return rc;
-    return check(hipStreamSynchronize(s), "hipStreamSynchronize");
+    CDA_TRY(launched("merkle levels"));
+    CDA_TRY(d2h(out, d_root, 32, s, "D2H"));
+    return sync(s);
 }
 
 }  // namespace cda

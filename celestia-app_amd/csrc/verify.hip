@@ -376,19 +376,15 @@ int Engine::share_proofs_verify(const cda_share_proof_batch* b, uint8_t* verdict
                 p_aunts = piece(rows ? b->aunts : nullptr, (size_t)b->n_aunts * 32),
                 p_lo = piece(leaf_off.data(), (size_t)(S + 1) * 8),
                 p_sh = piece(nmt ? b->shares : nullptr, (size_t)n_shares * b->share_len);
-    int rc;
-    if ((rc = check(vp_in_.ensure(total + 16), "hipMalloc proof batch"))) return rc;
+    CDA_TRY(ensure(vp_in_, total + 16, "hipMalloc proof batch"));
     const size_t scr_nodes = ((size_t)n_shares * stride + 15) & ~(size_t)15;
     const size_t flags = ((size_t)S + 15) & ~(size_t)15;
     const size_t node_slots = fast && nmt ? (size_t)b->n_nodes * kSlot : 0;
-    if ((rc = check(vp_scratch_.ensure(2 * scr_nodes + node_slots + 2 * flags + P + 16), "hipMalloc proof scratch")))
-        return rc;
+    CDA_TRY(ensure(vp_scratch_, 2 * scr_nodes + node_slots + 2 * flags + P + 16, "hipMalloc proof scratch"));
     uint8_t* in = vp_in_.as<uint8_t>();
     for (const Piece* pc : {&p_roots, &p_ns, &p_seg, &p_sp, &p_st, &p_en, &p_no, &p_nodes, &p_rr, &p_tot, &p_idx, &p_lh,
                             &p_ao, &p_aunts, &p_lo, &p_sh})
-        if (pc->bytes &&
-            (rc = check(hipMemcpyAsync(in + pc->off, pc->host, pc->bytes, hipMemcpyHostToDevice, s), "H2D proof batch")))
-            return rc;
+        if (pc->bytes) CDA_TRY(h2d(in + pc->off, pc->host, pc->bytes, s, "H2D proof batch"));
     auto dev = [&](const Piece& pc) -> const uint8_t* { return pc.host ? in + pc.off : nullptr; };
     uint8_t* scr = vp_scratch_.as<uint8_t>();
     VerifyBatch v{};
@@ -425,20 +421,20 @@ int Engine::share_proofs_verify(const cda_share_proof_batch* b, uint8_t* verdict
         const dim3 grid((uint32_t)((n_shares + 255) / 256));
         if (fast) hipLaunchKernelGGL(vp_leaf_kernel<true>, grid, dim3(256), 0, s, v);
         else hipLaunchKernelGGL(vp_leaf_kernel<false>, grid, dim3(256), 0, s, v);
-        if ((rc = check(hipGetLastError(), "proof leaves"))) return rc;
+        CDA_TRY(launched("proof leaves"));
         if (fast) hipLaunchKernelGGL(vp_fold_kernel<true>, dim3(S), dim3(64), 0, s, v);
         else hipLaunchKernelGGL(vp_fold_kernel<false>, dim3(S), dim3(64), 0, s, v);
-        if ((rc = check(hipGetLastError(), "proof range fold"))) return rc;
+        CDA_TRY(launched("proof range fold"));
     }
     if (rows && S) {
         hipLaunchKernelGGL(vp_row_kernel, dim3((S + 255) / 256), dim3(256), 0, s, v);
-        if ((rc = check(hipGetLastError(), "row proofs"))) return rc;
+        CDA_TRY(launched("row proofs"));
     }
     hipLaunchKernelGGL(vp_verdict_kernel, dim3((P + 255) / 256), dim3(256), 0, s, v);
-    if ((rc = check(hipGetLastError(), "proof verdicts"))) return rc;
+    CDA_TRY(launched("proof verdicts"));
     std::vector<uint8_t> out(P);
-    if ((rc = check(hipMemcpyAsync(out.data(), v.verdict, P, hipMemcpyDeviceToHost, s), "D2H verdicts"))) return rc;
-    if ((rc = check(hipStreamSynchronize(s), "hipStreamSynchronize"))) return rc;
+    CDA_TRY(d2h(out.data(), v.verdict, P, s, "D2H verdicts"));
+    CDA_TRY(sync(s));
     memcpy(verdict, out.data(), P);
     return CDA_OK;
 }
