@@ -69,6 +69,7 @@ EXPORTED = (
     "cda_comm_unique_id", "cda_comm_init", "cda_comm_destroy", "cda_comm_size", "cda_comm_abort", "cda_extend_dah_split", "cda_split_rows_send",
     "cda_extend_dah_multi", "cda_split_layout", "cda_split_offsets", "cda_extend_dah_batch_ex",
     "cda_share_proofs_verify", "cda_square_sample_proofs", "cda_sample_proofs_verify",
+    "cda_square_share_proofs_plan", "cda_square_share_proofs", "cda_square_tx_share_ranges",
 )
 # cda_square_sample_proofs axes (include/cda.h)
 CDA_AXIS_ROW = 0
@@ -129,6 +130,23 @@ class ShareProofBatch(C.Structure):
                 ("shares", _u8p), ("n_shares", C.c_uint64)]
 
 
+class ShareProofsPlanT(C.Structure):
+    """cda_share_proofs_plan_t (include/cda.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("n_segments", "n_nodes", "n_aunts", "aunts_per_segment")] + \
+               [("n_shares", C.c_uint64)]
+
+
+class ShareProofsOut(C.Structure):
+    """cda_share_proofs_out (include/cda.h): the arrays of ShareProofBatch, writable, plus the proofs' rows and
+    the one_namespace flags."""
+    _u8p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    _i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    _fields_ = [("seg_off", _u32p), ("nmt_start", _i32p), ("nmt_end", _i32p), ("node_off", _u32p),
+                ("nodes", _u8p), ("row_roots", _u8p), ("rfc_total", _i64p), ("rfc_index", _i64p),
+                ("rfc_leaf_hash", _u8p), ("aunt_off", _u32p), ("aunts", _u8p), ("shares", _u8p),
+                ("namespaces", _u8p), ("start_row", _u32p), ("end_row", _u32p), ("one_namespace", _u8p)]
+
+
 _lib = None
 _libs = {}
 _lock = threading.RLock()   # re-entrant: default_context() creates a Context (load()) under it
@@ -185,6 +203,8 @@ def load(path: str | None = None):
                                         u32p, u32p, C.c_uint32, u32p]
         L.cda_square_tx_share_range.argtypes = [ctxp, u8p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                                 u32p, u32p, C.POINTER(C.c_int)]
+        L.cda_square_tx_share_ranges.argtypes = [ctxp, u8p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, u32p,
+                                                 C.c_uint32, u32p, u32p, u8p]
         L.cda_square_construct.argtypes = [ctxp, u8p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u8p,
                                            C.c_size_t, u32p, u32p, u32p]
         L.cda_construct_extend_dah.argtypes = [ctxp, u8p, u64p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, u8p,
@@ -213,6 +233,8 @@ def load(path: str | None = None):
         L.cda_square_sample_proofs.argtypes = [vp, u32p, u32p, u8p, C.c_uint32, u8p, u8p, u8p, u8p, u8p, u8p]
         L.cda_sample_proofs_verify.argtypes = [ctxp, C.c_uint32, C.c_uint32, u8p, u32p, u32p, u8p, u8p, u8p, u8p,
                                                u8p, u8p, u8p]
+        L.cda_square_share_proofs_plan.argtypes = [C.c_uint32, u32p, u32p, C.c_uint32, C.POINTER(ShareProofsPlanT)]
+        L.cda_square_share_proofs.argtypes = [vp, u32p, u32p, C.c_uint32, C.POINTER(ShareProofsOut)]
         L.cda_comm_unique_id.argtypes = [u8p]
         L.cda_comm_init.argtypes = [ctxp, C.c_int, C.c_int, u8p]
         L.cda_comm_destroy.argtypes = [ctxp]

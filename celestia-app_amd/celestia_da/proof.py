@@ -5,7 +5,9 @@ Reference: pkg/proof/proof.go:22-206 (NewTxInclusionProof,
 NewShareInclusionProof, NewShareInclusionProofFromEDS), pkg/proof/proof.pb.go (ShareProof,
 RowProof, NMTProof, Proof field names), pkg/inclusion/get_commit.go:12-30.
 The square is extended once (`ResidentSquare`); the EDS, every row-tree
-level and the data-root tree stay in HBM, so each proof is a gather.
+level and the data-root tree stay in HBM, so each proof is a gather; the
+proofs of many ranges come from one launch as the flat batch the verifier
+takes (`ResidentSquare.share_proofs_batch`, `ShareProofsBatch`).
 """
 from __future__ import annotations
 
@@ -210,6 +212,20 @@ class ResidentSquare:
                           row_proof=RowProof([rb[90 * i:90 * (i + 1)] for i in range(R)], proofs, r0.value, r1.value),
                           namespace_version=namespace[0])
 
+    def share_proofs_batch(self, ranges, out=None) -> "ShareProofsBatch":
+        """NewShareInclusionProofFromEDS for every (start, end) of `ranges` in
+        one cda_square_share_proofs call (one launch): a ShareProofsBatch.
+        out: a ShareProofsBatch.empty(k, ranges) to fill instead of a new one."""
+        r = _ranges_array(ranges)
+        if out is None:
+            out = ShareProofsBatch.empty(self.k, r)
+        starts, ends = np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+        u32p = C.POINTER(C.c_uint32)
+        o = out.out_struct()
+        self.ctx.check(self.ctx.lib.cda_square_share_proofs(self.h, starts.ctypes.data_as(u32p),
+                                                            ends.ctypes.data_as(u32p), len(r), C.byref(o)))
+        return out
+
     def sample_proofs(self, coords, out=None):
         """Data-availability samples of the EDS (cda_square_sample_proofs):
         coords is an (n, 3) integer array of (row, col, axis), 0 <= row, col <
@@ -237,6 +253,145 @@ class ResidentSquare:
         out = np.empty(90, dtype=np.uint8)
         self.ctx.check(self.ctx.lib.cda_square_subtree_root(self.h, row, ptr(w), len(walk), ptr(out)))
         return out.tobytes()
+
+
+# ------------------------------------------------- proofs of many ranges at once
+def _ranges_array(ranges) -> np.ndarray:
+    """(n, 2) uint32 array of (start, end)."""
+    r = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    if r.size and (r.min() < 0 or r.max() >= 1 << 32):
+        raise _lib.CdaError(_lib.CDA_ERR_INVALID, "share range out of the original square")
+    return r.astype(np.uint32)
+
+
+def share_proofs_plan(k: int, ranges) -> dict:
+    """cda_square_share_proofs_plan: the sizes of the batch of `ranges` of a
+    square of ODS width k -- n_segments, n_nodes, n_aunts, aunts_per_segment,
+    n_shares.  Host only, no context; CdaError names the range and the field."""
+    r = _ranges_array(ranges)
+    L = _lib.load()
+    starts, ends = np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+    u32p = C.POINTER(C.c_uint32)
+    p = _lib.ShareProofsPlanT()
+    rc = L.cda_square_share_proofs_plan(k, starts.ctypes.data_as(u32p), ends.ctypes.data_as(u32p), len(r), C.byref(p))
+    if rc != _lib.CDA_OK:
+        raise _lib.CdaError(rc, L.cda_last_error(None).decode())
+    return {n: getattr(p, n) for n, _ in _lib.ShareProofsPlanT._fields_}
+
+
+class ShareProofsBatch:
+    """The share proofs of n ranges of one square as the flat arrays of
+    cda_share_proofs_out (numpy; include/cda.h): proof i owns the segments
+    (rows) seg_off[i] .. seg_off[i + 1], segment g the nodes node_off[g] ..
+    node_off[g + 1] and the aunts aunt_off[g] .. aunt_off[g + 1]; the shares
+    are concatenated in proof then segment order."""
+
+    FIELDS = ("seg_off", "nmt_start", "nmt_end", "node_off", "nodes", "row_roots", "rfc_total", "rfc_index",
+              "rfc_leaf_hash", "aunt_off", "aunts", "shares", "namespaces", "start_row", "end_row", "one_namespace")
+
+    def __init__(self, k, ranges, **arrays):
+        self.k, self.ranges = k, ranges
+        for name in self.FIELDS:
+            setattr(self, name, arrays[name])
+
+    @classmethod
+    def empty(cls, k, ranges, fill=None):
+        """Buffers of the plan's sizes (filled with the byte `fill` if given)."""
+        r = _ranges_array(ranges)
+        p = share_proofs_plan(k, r)
+        n, S = len(r), p["n_segments"]
+        shapes = {"seg_off": ((n + 1,), np.uint32), "nmt_start": ((S,), np.int32), "nmt_end": ((S,), np.int32),
+                  "node_off": ((S + 1,), np.uint32), "nodes": ((p["n_nodes"], NMT_ROOT_SIZE), np.uint8),
+                  "row_roots": ((S, NMT_ROOT_SIZE), np.uint8), "rfc_total": ((S,), np.int64),
+                  "rfc_index": ((S,), np.int64), "rfc_leaf_hash": ((S, 32), np.uint8),
+                  "aunt_off": ((S + 1,), np.uint32), "aunts": ((p["n_aunts"], 32), np.uint8),
+                  "shares": ((p["n_shares"], SHARE_SIZE), np.uint8), "namespaces": ((n, 29), np.uint8),
+                  "start_row": ((n,), np.uint32), "end_row": ((n,), np.uint32), "one_namespace": ((n,), np.uint8)}
+        arrays = {}
+        for name, (shape, dtype) in shapes.items():
+            a = np.empty(shape, dtype=dtype)
+            if fill is not None:
+                a.view(np.uint8).fill(fill)
+            arrays[name] = a
+        return cls(k, r, **arrays)
+
+    def __len__(self):
+        return len(self.ranges)
+
+    def arrays(self):
+        return tuple(getattr(self, name) for name in self.FIELDS)
+
+    def out_struct(self, skip=()):
+        """cda_share_proofs_out over the arrays (NULL for the names in `skip`)."""
+        o = _lib.ShareProofsOut()
+        for (name, t), a in zip(_lib.ShareProofsOut._fields_, self.arrays()):
+            assert name in self.FIELDS
+            if name not in skip:
+                setattr(o, name, a.ctypes.data_as(t))
+        return o
+
+    def batch(self, data_root):
+        """The cda_share_proof_batch for cda_share_proofs_verify over these
+        arrays, unchanged: pointer assignment, no per-proof objects.
+        data_root: 32 bytes for every proof, or n * 32."""
+        n = len(self)
+        roots = np.frombuffer(bytes(data_root), dtype=np.uint8) if isinstance(data_root, (bytes, bytearray)) \
+            else np.ascontiguousarray(data_root, dtype=np.uint8).reshape(-1)
+        if roots.size == 32:
+            roots = np.tile(roots, max(1, n))
+        if roots.size != 32 * max(1, n):
+            raise ValueError(f"{n} proofs but {roots.size} bytes of data roots")
+        b = _lib.ShareProofBatch()
+        b.n_proofs, b.ns_len, b.share_len = n, 29, SHARE_SIZE
+        b.data_roots = roots.ctypes.data_as(_lib.ShareProofBatch._u8p)
+        for name, t in _lib.ShareProofBatch._fields_:
+            if name in self.FIELDS:
+                setattr(b, name, getattr(self, name).ctypes.data_as(t))
+        b.n_nodes, b.n_aunts, b.n_shares = len(self.nodes), len(self.aunts), len(self.shares)
+        b._keep = (roots, self)   # the struct borrows the arrays
+        return b
+
+    def verify(self, data_root, ctx=None) -> np.ndarray:
+        """cda_share_proofs_verify of the batch: verdict per proof (0 valid, 1
+        row proof, 2 share proof)."""
+        ctx = ctx or default_context()
+        b = self.batch(data_root)
+        verdict = np.full(max(1, len(self)), 255, dtype=np.uint8)
+        ctx.check(ctx.lib.cda_share_proofs_verify(ctx.h, C.byref(b), ptr(verdict)))
+        return verdict[:len(self)]
+
+    def proofs(self, namespaces=None) -> list:
+        """One ShareProof per range, equal field for field to
+        ResidentSquare.share_proof(namespace, start, end).  namespaces: one
+        29-byte namespace per range; None takes the first share's, and a range
+        whose shares carry more than one namespace raises ParseNamespace's
+        error (ValueError), computed from the returned shares."""
+        W = 2 * self.k
+        nb, rb, lb, ab, sb = (a.tobytes() for a in (self.nodes, self.row_roots, self.rfc_leaf_hash, self.aunts,
+                                                    self.shares))
+        seg_off, node_off, aunt_off = self.seg_off.tolist(), self.node_off.tolist(), self.aunt_off.tolist()
+        st, en, idx = self.nmt_start.tolist(), self.nmt_end.tolist(), self.rfc_index.tolist()
+        r0, r1 = self.start_row.tolist(), self.end_row.tolist()
+        cut = lambda b, lo, hi, sz: [b[i * sz:(i + 1) * sz] for i in range(lo, hi)]  # noqa: E731
+        out, share_at = [], 0
+        for i in range(len(self)):
+            segs = range(seg_off[i], seg_off[i + 1])
+            n_sh = sum(en[g] - st[g] for g in segs)
+            data = cut(sb, share_at, share_at + n_sh, SHARE_SIZE)
+            share_at += n_sh
+            if namespaces is None:
+                if not self.one_namespace[i]:
+                    parse_namespace(data, 0, len(data))
+                ns = self.namespaces[i].tobytes()
+            else:
+                ns = bytes(namespaces[i])
+            sp = [NMTProof(st[g], en[g], cut(nb, node_off[g], node_off[g + 1], NMT_ROOT_SIZE)) for g in segs]
+            rp = [Proof(2 * W, idx[g], lb[32 * g:32 * (g + 1)], cut(ab, aunt_off[g], aunt_off[g + 1], 32))
+                  for g in segs]
+            out.append(ShareProof(data=data, share_proofs=sp, namespace_id=ns[1:],
+                                  row_proof=RowProof(cut(rb, segs.start, segs.stop, NMT_ROOT_SIZE), rp, r0[i], r1[i]),
+                                  namespace_version=ns[0]))
+        return out
 
 
 # ------------------------------------------------------------ verification
@@ -419,6 +574,27 @@ def tx_share_range(txs, tx_index: int, max_square_size: int = 128, subtree_root_
     return s.value, e.value, PAY_FOR_BLOB_NAMESPACE if pfb.value else TX_NAMESPACE
 
 
+def tx_share_ranges(txs, tx_indexes, max_square_size: int = 128, subtree_root_threshold: int = 64) -> list:
+    """tx_share_range for every index of tx_indexes, with the square laid out
+    once (cda_square_tx_share_ranges): a list of (start, end, namespace).
+    Host only."""
+    from .square import _flatten, _u64p
+    L = _lib.load()
+    buf, off = _flatten(txs)
+    idx = np.ascontiguousarray(tx_indexes, dtype=np.uint32)
+    n = idx.size
+    s, e, pfb = np.empty(max(1, n), dtype=np.uint32), np.empty(max(1, n), dtype=np.uint32), \
+        np.empty(max(1, n), dtype=np.uint8)
+    u32p = C.POINTER(C.c_uint32)
+    rc = L.cda_square_tx_share_ranges(None, ptr(buf), _u64p(off), len(txs), max_square_size, subtree_root_threshold,
+                                      idx.ctypes.data_as(u32p), n, s.ctypes.data_as(u32p), e.ctypes.data_as(u32p),
+                                      ptr(pfb))
+    if rc != _lib.CDA_OK:
+        msg = L.cda_last_error(None).decode()
+        raise (_lib.SquareError if rc == _lib.CDA_ERR_SQUARE else _lib.CdaError)(rc, msg)
+    return [(int(s[i]), int(e[i]), PAY_FOR_BLOB_NAMESPACE if pfb[i] else TX_NAMESPACE) for i in range(n)]
+
+
 def new_share_inclusion_proof(ods, namespace: bytes, start: int, end: int, ctx=None) -> ShareProof:
     """NewShareInclusionProof (proof.go:59-73): extend the square, prove the
     range.  ods: the square's shares (bytes, a list of shares or an array)."""
@@ -445,6 +621,40 @@ def new_tx_inclusion_proof(txs, tx_index: int, app_version: int = 2, ctx=None) -
     start, end, ns = tx_share_range(txs, tx_index, ub, thr)
     sq = square.construct(txs, ub, thr, ctx=ctx)
     return new_share_inclusion_proof(sq.to_bytes(), ns, start, end, ctx)
+
+
+def new_share_inclusion_proofs(ods, ranges, namespaces=None, ctx=None) -> list:
+    """NewShareInclusionProof for every (start, end) of `ranges` over one
+    square: one extension and one batch call (ResidentSquare.
+    share_proofs_batch).  namespaces: as ShareProofsBatch.proofs."""
+    if isinstance(ods, (bytes, bytearray, memoryview)):
+        ods = np.frombuffer(ods, dtype=np.uint8)
+    elif isinstance(ods, list):
+        ods = np.frombuffer(b"".join(ods), dtype=np.uint8)
+    sq = ResidentSquare(ods, ctx)
+    try:
+        return sq.share_proofs_batch(ranges).proofs(namespaces)
+    finally:
+        sq.close()
+
+
+def new_tx_inclusion_proofs(txs, indexes=None, app_version: int = 2, ctx=None) -> list:
+    """NewTxInclusionProof for the transactions `indexes` of a block (None:
+    every transaction): one square.Construct, one resident square and one
+    batch call; equal to [new_tx_inclusion_proof(txs, i) for i in indexes]."""
+    from . import square
+    indexes = list(range(len(txs))) if indexes is None else [int(i) for i in indexes]
+    for i in indexes:
+        if i < 0:   # the Go parameter is a uint64
+            raise _lib.CdaError(_lib.CDA_ERR_INVALID, f"txIndex {i} is negative")
+        if i >= len(txs):
+            raise _lib.CdaError(_lib.CDA_ERR_INVALID, f"txIndex {i} out of bounds")
+    if not indexes:
+        return []
+    ub, thr = square.SQUARE_SIZE_UPPER_BOUND, square.SUBTREE_ROOT_THRESHOLD   # appconsts, every version
+    found = tx_share_ranges(txs, indexes, ub, thr)
+    sq = square.construct(txs, ub, thr, ctx=ctx)
+    return new_share_inclusion_proofs(sq.to_bytes(), [(s, e) for s, e, _ in found], [ns for _, _, ns in found], ctx)
 
 
 def _parse_int64(text: str) -> int:

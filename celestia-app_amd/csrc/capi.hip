@@ -10,6 +10,7 @@
 
 #include "../../include/cda.h"
 #include "engine.h"
+#include "share_proofs_plan.h"
 #include "split_layout.h"
 
 struct cda_ctx {
@@ -384,6 +385,35 @@ int cda_square_tx_share_range(cda_ctx* ctx, const uint8_t* txs, const uint64_t* 
     return host_only(ctx, run);
 }
 
+int cda_square_tx_share_ranges(cda_ctx* ctx, const uint8_t* txs, const uint64_t* tx_off, uint32_t n_txs,
+                               uint32_t max_square_size, uint32_t threshold, const uint32_t* tx_indexes, uint32_t n,
+                               uint32_t* starts, uint32_t* ends, uint8_t* is_pfb) {
+    // Host-only (no device work): usable without a context.
+    auto run = [&](std::string* err) -> int {
+        if ((n && (!tx_indexes || !starts || !ends)) || (n_txs && (!txs || !tx_off))) {
+            *err = "null buffer";
+            return CDA_ERR_INVALID;
+        }
+        cda::square::Plan p;
+        if (plan_square(txs, tx_off, n_txs, max_square_size, threshold, CDA_SQUARE_CONSTRUCT, &p, err))
+            return CDA_ERR_SQUARE;
+        for (uint32_t i = 0; i < n; i++)
+            if (tx_indexes[i] >= p.unit_start.size()) {
+                char b[64];
+                snprintf(b, sizeof b, "txIndex %u out of range", tx_indexes[i]);
+                *err = b;
+                return CDA_ERR_INVALID;
+            }
+        for (uint32_t i = 0; i < n; i++) {
+            starts[i] = p.unit_start[tx_indexes[i]];
+            ends[i] = p.unit_end[tx_indexes[i]];
+            if (is_pfb) is_pfb[i] = tx_indexes[i] >= p.n_normal;
+        }
+        return CDA_OK;
+    };
+    return host_only(ctx, run);
+}
+
 int cda_square_layout(cda_ctx* ctx, const uint8_t* txs, const uint64_t* tx_off, uint32_t n_txs,
                       uint32_t max_square_size, uint32_t threshold, int mode, uint32_t* square_size, uint32_t* kept,
                       uint32_t* n_kept, uint32_t* share_indexes, uint32_t share_index_cap, uint32_t* n_share_indexes) {
@@ -579,6 +609,31 @@ int cda_square_sample_proofs(cda_square* sq, const uint32_t* rows, const uint32_
     return guarded(sq->ctx, [&](cda::Engine& e) -> int {
         const cda::Engine::SampleOut o{shares, namespaces, nmt_nodes, axis_roots, leaf_hash, aunts};
         return e.square_sample_proofs(&sq->sq, rows, cols, axes, n, o);
+    });
+}
+
+int cda_square_share_proofs_plan(uint32_t k, const uint32_t* starts, const uint32_t* ends, uint32_t n,
+                                 cda_share_proofs_plan_t* out) {
+    // Host-only (no device work), no context.
+    return host_only(nullptr, [&](std::string* err) -> int {
+        if (!out) {
+            *err = "null buffer";
+            return CDA_ERR_INVALID;
+        }
+        cda::ShareProofsPlan p;
+        *err = cda::share_proofs_plan(k, starts, ends, n, &p);
+        if (!err->empty()) return CDA_ERR_INVALID;
+        *out = cda_share_proofs_plan_t{p.n_segments, p.n_nodes, p.n_aunts, p.aunts_per_segment, p.n_shares};
+        return CDA_OK;
+    });
+}
+
+int cda_square_share_proofs(cda_square* sq, const uint32_t* starts, const uint32_t* ends, uint32_t n,
+                            const cda_share_proofs_out* out) {
+    if (!sq) return CDA_ERR_INVALID;
+    return guarded(sq->ctx, [&](cda::Engine& e) -> int {
+        if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.square_share_proofs(&sq->sq, starts, ends, n, *out);
     });
 }
 

@@ -16,6 +16,7 @@
 #include "square_plan.h"
 
 struct cda_share_proof_batch;   // include/cda.h
+struct cda_share_proofs_out;
 
 // The one early-return form of the host code: a non-zero CDA_* code leaves the function.
 #define CDA_TRY(expr)                     \
@@ -293,6 +294,10 @@ class Engine {
     };
     int square_sample_proofs(ResidentSquare* sq, const uint32_t* rows, const uint32_t* cols, const uint8_t* axes,
                              uint32_t n, const SampleOut& out);
+    // Share-inclusion proofs of n ranges [starts[i], ends[i]) of the ODS in one launch (share_proofs.hip),
+    // laid out as the batch of share_proofs_verify; any output may be NULL (include/cda.h).
+    int square_share_proofs(ResidentSquare* sq, const uint32_t* starts, const uint32_t* ends, uint32_t n,
+                            const cda_share_proofs_out& out);
     // The verifying side: the batch of share_proofs_verify built from the coordinates.
     int sample_proofs_verify(uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
                              const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,

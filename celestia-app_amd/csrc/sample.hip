@@ -34,6 +34,7 @@
 
 #include "../../include/cda.h"
 #include "engine.h"
+#include "packed_store_dev.h"
 #include "sha256_dev.h"
 #include "tree_index.h"
 
@@ -60,41 +61,6 @@ struct SampleArgs {
     uint8_t* leaf_hash;
     uint8_t* aunts;
 };
-
-// `count` items of ITEM bytes, held in LDS at a stride of kSlot bytes, to the
-// packed bytes dst[0 : count * ITEM) at any address: whole aligned words by one
-// 4-byte store per lane, the bytes of a word that the region only partly covers
-// singly (a neighbouring sample owns the rest of that word).
-template <uint32_t ITEM>
-__device__ __forceinline__ void store_packed(const uint8_t* lds, uint32_t count, uint8_t* dst, uint32_t lane) {
-    const uint32_t len = count * ITEM;
-    const uint32_t a = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 3u);
-    const uint32_t n_words = (a + len + 3) / 4;
-    for (uint32_t w = lane; w < n_words; w += 64) {
-        const int32_t b0 = (int32_t)(4 * w) - (int32_t)a;
-        uint32_t v = 0;
-        bool full = true;
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int32_t b = b0 + t;
-            if (b >= 0 && b < (int32_t)len) {
-                const uint32_t item = (uint32_t)b / ITEM, o = (uint32_t)b % ITEM;
-                v |= (uint32_t)lds[item * kSlot + o] << (8 * t);
-            } else {
-                full = false;
-            }
-        }
-        if (full) {
-            *reinterpret_cast<uint32_t*>(dst + b0) = v;
-        } else {
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                const int32_t b = b0 + t;
-                if (b >= 0 && b < (int32_t)len) dst[b] = (uint8_t)(v >> (8 * t));
-            }
-        }
-    }
-}
 
 __global__ __launch_bounds__(64 * kSampleWaves) void sample_kernel(const SampleArgs a) {
     __shared__ uint4 stage[kSampleWaves][kSampleSlots * (kSlot / 16)];

@@ -1,7 +1,8 @@
 // tree_index.h -- index arithmetic of the proof paths: which nodes of a
 // Merkle tree a range proof takes and where a level of a resident square's
 // trees lies.  Plain C++ (no HIP headers), so a host compiler builds and tests
-// it (tools/tree_index_host_test.cpp); level_offset is also device code.
+// it (tools/tree_index_host_test.cpp, tools/range_proof_host_test.cpp);
+// level_offset and the closed-form range proof are also device code.
 //
 // The trees pair adjacent nodes level by level and promote an odd last node
 // unchanged, which builds the RFC-6962 tree (split at the largest power of two
@@ -60,6 +61,53 @@ CDA_INDEX_HD constexpr uint64_t level_offset(uint32_t W, uint32_t L, uint32_t fi
     uint64_t off = 0;
     for (uint32_t l = first; l < L; l++) off += (uint64_t)W * (W >> l) * slot;
     return off;
+}
+
+// The closed form of prove_nodes for a perfect tree of 2^D leaves (a resident
+// square's row trees), usable on the device: the proof of [s, e), 0 <= s < e
+// <= 2^D, lists
+//   left of the range:  for every set bit L of s, from L = D - 1 down to 0,
+//                       node (s >> L) - 1 of level L;
+//   right of the range: for every clear bit L of e - 1, from L = 0 up to
+//                       D - 1, node ((e - 1) >> L) + 1 of level L.
+// For e = s + 1 this is the sibling rule of sample.hip.  prove_nodes (any leaf
+// count) is the check: tools/range_proof_host_test.cpp.
+CDA_INDEX_HD constexpr uint32_t popcount32(uint32_t x) {
+    x = x - ((x >> 1) & 0x55555555u);
+    x = (x & 0x33333333u) + ((x >> 2) & 0x33333333u);
+    return (((x + (x >> 4)) & 0x0F0F0F0Fu) * 0x01010101u) >> 24;
+}
+
+CDA_INDEX_HD constexpr uint32_t range_proof_count(uint32_t D, uint32_t s, uint32_t e) {
+    return popcount32(s) + D - popcount32(e - 1);
+}
+
+struct TreeNode {
+    uint32_t level, index;
+};
+
+// Node q of that proof, q < range_proof_count(D, s, e).  Every level is
+// visited whatever q is, so lanes of one wavefront that ask for different q of
+// the same range run the same instructions.
+CDA_INDEX_HD constexpr TreeNode range_proof_node(uint32_t D, uint32_t s, uint32_t e, uint32_t q) {
+    const uint32_t n_left = popcount32(s), last = e - 1;
+    TreeNode node{0, 0};
+    uint32_t seen = 0;
+    for (uint32_t i = 0; i < D; i++) {   // left nodes, top down
+        const uint32_t L = D - 1 - i;
+        if ((s >> L) & 1u) {
+            if (seen == q) node = TreeNode{L, (s >> L) - 1};
+            seen++;
+        }
+    }
+    seen = n_left;
+    for (uint32_t L = 0; L < D; L++) {   // right nodes, bottom up
+        if (!((last >> L) & 1u)) {
+            if (seen == q) node = TreeNode{L, (last >> L) + 1};
+            seen++;
+        }
+    }
+    return node;
 }
 
 }  // namespace cda

@@ -42,6 +42,9 @@
  *                          row or column tree (rsmt2d / wrapper trees,
  *                          pkg/wrapper/nmt_wrapper.go:55-129) and the merkle proof
  *                          of that root in the DAH; batched, and the batch check
+ *   cda_square_share_proofs / cda_square_share_proofs_plan
+ *                          NewShareInclusionProofFromEDS for many ranges of one
+ *                          square in one launch, as a cda_share_proof_batch
  *   cda_nmt_axis_root(s) / cda_nmt_prove_range
  *                          wrapper.NewErasuredNamespacedMerkleTree + Push +
  *                          Root / ProveRange (pkg/wrapper/nmt_wrapper.go:55-129)
@@ -359,6 +362,13 @@ int cda_square_tx_share_range(cda_ctx *ctx, const uint8_t *txs, const uint64_t *
                               uint32_t max_square_size, uint32_t threshold, uint32_t tx_index, uint32_t *start,
                               uint32_t *end, int *is_pfb);
 
+/* cda_square_tx_share_range for n kept txs at once: the square is laid out once, then starts[i],
+ * ends[i] and is_pfb[i] (n bytes, may be NULL) answer tx_indexes[i].  An index out of range fails
+ * the call as above, nothing written.  Host only; ctx may be NULL. */
+int cda_square_tx_share_ranges(cda_ctx *ctx, const uint8_t *txs, const uint64_t *tx_off, uint32_t n_txs,
+                               uint32_t max_square_size, uint32_t threshold, const uint32_t *tx_indexes, uint32_t n,
+                               uint32_t *starts, uint32_t *ends, uint8_t *is_pfb);
+
 /* The square's k*k shares (row-major) into ods (host, ods_capacity bytes;
  * max_square_size^2 * 512 always suffices).  Shares are written on the GPU. */
 int cda_square_construct(cda_ctx *ctx, const uint8_t *txs, const uint64_t *tx_off, uint32_t n_txs,
@@ -476,6 +486,62 @@ int cda_sample_proofs_verify(cda_ctx *ctx, uint32_t k, uint32_t n, const uint8_t
                              const uint32_t *rows, const uint32_t *cols, const uint8_t *axes,
                              const uint8_t *shares, const uint8_t *nmt_nodes, const uint8_t *axis_roots,
                              const uint8_t *leaf_hash, const uint8_t *aunts, uint8_t *verdict);
+
+/* ---- Share-inclusion proofs of many ranges in one launch -----------------------
+ * proof.NewShareInclusionProofFromEDS (pkg/proof/proof.go:77-145) for n ranges [starts[i], ends[i]) of
+ * the ODS of one resident square at once, in the flat layout of cda_share_proof_batch below: the
+ * arrays of cda_share_proofs_out carry that struct's field names and layouts, so a batch for
+ * cda_share_proofs_verify is filled from them by pointer assignment (ns_len 29, share_len 512,
+ * n_nodes / n_aunts / n_shares from the plan).  Proof i covers the rows start_row[i] .. end_row[i], one
+ * segment per row; S segments in all.
+ *
+ * cda_square_share_proofs_plan: host only, no context (the message of an error is
+ * cda_last_error(NULL) of the calling thread).  Checks the ranges and returns the sizes to allocate:
+ *   n_segments = S, n_nodes, n_aunts = S * aunts_per_segment (log2(4k) each), n_shares.
+ * CDA_ERR_INVALID, *out untouched, with a message naming the range and the field
+ * ("range 3: end 70 is beyond the 64 shares of the original square") for start >= end, end > k*k, or
+ * an offset that does not fit the batch's uint32_t offsets; also for k not a power of two <= 1024.
+ * n == 0: CDA_OK, all sizes zero. */
+typedef struct {
+    uint32_t n_segments, n_nodes, n_aunts, aunts_per_segment;
+    uint64_t n_shares;
+} cda_share_proofs_plan_t;
+int cda_square_share_proofs_plan(uint32_t k, const uint32_t *starts, const uint32_t *ends, uint32_t n,
+                                 cda_share_proofs_plan_t *out);
+/* Caller-allocated host buffers, any of them NULL (sizes from the plan).
+ * Written by the host:
+ *   seg_off n+1; nmt_start / nmt_end S; node_off S+1; aunt_off S+1; rfc_total S (all 4k);
+ *   rfc_index S (the row); start_row / end_row n.
+ * Written by the kernel:
+ *   nodes n_nodes*90 (nmt ProveRange order per segment, packed); row_roots S*90; rfc_leaf_hash S*32;
+ *   aunts n_aunts*32 (bottom-up); shares n_shares*512 (proof then segment order);
+ *   namespaces n*29 (the first share's namespace);
+ *   one_namespace n bytes: 1 if every share of the range carries the first share's namespace (what
+ *   proof.ParseNamespace tests, pkg/proof/querier.go:134-166), else 0. */
+typedef struct cda_share_proofs_out {
+    uint32_t *seg_off;
+    int32_t *nmt_start;
+    int32_t *nmt_end;
+    uint32_t *node_off;
+    uint8_t *nodes;
+    uint8_t *row_roots;
+    int64_t *rfc_total;
+    int64_t *rfc_index;
+    uint8_t *rfc_leaf_hash;
+    uint32_t *aunt_off;
+    uint8_t *aunts;
+    uint8_t *shares;
+    uint8_t *namespaces;
+    uint32_t *start_row;
+    uint32_t *end_row;
+    uint8_t *one_namespace;
+} cda_share_proofs_out;
+/* The ranges are checked as by the plan before anything is enqueued (CDA_ERR_INVALID, outputs
+ * untouched).  One kernel launch per call, whatever n and the ranges' lengths; host buffers, complete
+ * when the call returns.  A square created with CDA_ERR_PUSH_ORDER serves proofs like any other.
+ * cda_square_share_proof returns the same bytes for one range per call. */
+int cda_square_share_proofs(cda_square *sq, const uint32_t *starts, const uint32_t *ends, uint32_t n,
+                            const cda_share_proofs_out *out);
 
 /* ---- Repair ------------------------------------------
  * rsmt2d ExtendedDataSquare.Repair(rowRoots, colRoots) (EXT v0.14.0,
