@@ -576,12 +576,11 @@ int cda_square_share_proof(cda_square* sq, uint32_t start, uint32_t end, uint8_t
     return guarded(sq->ctx, [&](cda::Engine& e) -> int {
         if (!nmt_start || !nmt_end || !nmt_count || !start_row || !end_row)
             return e.fail(CDA_ERR_INVALID, "null buffer");
-        cda::Engine::ShareProofOut o{shares, 0, 0, nmt_start, nmt_end, nmt_count, nmt_nodes, row_roots,
-                                     row_leaf_hash, row_aunts};
-        const int rc = e.square_share_proof(&sq->sq, start, end, &o);
-        *start_row = o.start_row;
-        *end_row = o.end_row;
-        return rc;
+        *start_row = *end_row = 0;   // what a failed call leaves in them
+        const cda_share_proofs_out o{.nmt_start = nmt_start, .nmt_end = nmt_end, .nodes = nmt_nodes,
+                                     .row_roots = row_roots, .rfc_leaf_hash = row_leaf_hash, .aunts = row_aunts,
+                                     .shares = shares, .start_row = start_row, .end_row = end_row};
+        return e.square_share_proof(&sq->sq, start, end, o, nmt_count);
     });
 }
 

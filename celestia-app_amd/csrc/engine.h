@@ -17,6 +17,10 @@
 
 struct cda_share_proof_batch;   // include/cda.h
 struct cda_share_proofs_out;
+namespace cda {
+class OutRegions;      // out_regions.h
+struct ResidentView;   // resident_proof_dev.h
+}
 
 // The one early-return form of the host code: a non-zero CDA_* code leaves the function.
 #define CDA_TRY(expr)                     \
@@ -112,13 +116,13 @@ struct ResidentSquare {
     DevBuf eds, levels, col_levels, roots_slots, rfc, rows, cols, root, err, scratch, pieces;
     uint64_t level_offset(uint32_t L) const;       // bytes into `levels`, L >= 0
     uint64_t col_level_offset(uint32_t L) const;   // bytes into `col_levels`, L >= 1
+    ResidentView view() const;                     // what the proof kernels read
     ~ResidentSquare();
 };
-// One copy out of a resident square (byte offsets into the named buffer).
+// One copy out of a resident square: len bytes at src (device) to byte dst of the gathered output.
 struct GatherPiece {
-    enum Buf : uint32_t { kEds = 0, kLevels = 1, kRfc = 2, kRows = 3, kRootSlots = 4 };
-    uint32_t buf;
-    uint64_t src, dst;
+    const uint8_t* src;
+    uint64_t dst;
     uint32_t len;
 };
 
@@ -267,18 +271,6 @@ class Engine {
     int square_gather(ResidentSquare* sq, const std::vector<GatherPiece>& pieces, uint8_t* out, size_t out_len);
     int square_gather_device(ResidentSquare* sq, const std::vector<GatherPiece>& pieces, size_t out_len);
     int square_read(ResidentSquare* sq, ResidentSquare::Part part, uint8_t* out);   // synchronous D2H
-    struct ShareProofOut {
-        uint8_t* shares;
-        uint32_t start_row, end_row;
-        int32_t* nmt_start;
-        int32_t* nmt_end;
-        uint32_t* nmt_count;
-        uint8_t* nmt_nodes;       // [rows][2 log2(2k)][90]
-        uint8_t* row_roots;       // [rows][90]
-        uint8_t* row_leaf_hash;   // [rows][32]
-        uint8_t* row_aunts;       // [rows][log2(4k)][32]
-    };
-    int square_share_proof(ResidentSquare* sq, uint32_t start, uint32_t end, ShareProofOut* out);
     int square_subtree_root(ResidentSquare* sq, uint32_t row, const uint8_t* walk, uint32_t walk_len, uint8_t* out);
     int square_blob_commitments(ResidentSquare* sq, const uint32_t* starts, const uint32_t* lens, uint32_t n,
                                 uint32_t threshold, uint8_t* out);
@@ -296,8 +288,13 @@ class Engine {
                              uint32_t n, const SampleOut& out);
     // Share-inclusion proofs of n ranges [starts[i], ends[i]) of the ODS in one launch (share_proofs.hip),
     // laid out as the batch of share_proofs_verify; any output may be NULL (include/cda.h).
+    // nmt_count, one_copy_max: the single-range call's layout of the nodes and its copy back.
     int square_share_proofs(ResidentSquare* sq, const uint32_t* starts, const uint32_t* ends, uint32_t n,
-                            const cda_share_proofs_out& out);
+                            const cda_share_proofs_out& out, uint32_t* nmt_count = nullptr, size_t one_copy_max = 0);
+    // The same for one range, in the layout of cda_square_share_proof: out.nodes holds 2 log2(2k) slots per
+    // row, nmt_count[i] of row i's valid.
+    int square_share_proof(ResidentSquare* sq, uint32_t start, uint32_t end, const cda_share_proofs_out& out,
+                           uint32_t* nmt_count);
     // The verifying side: the batch of share_proofs_verify built from the coordinates.
     int sample_proofs_verify(uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
                              const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,
@@ -351,6 +348,9 @@ class Engine {
     }
     int launched(const char* what) { return check(hipGetLastError(), what); }   // after a <<<>>> launch
     int sync(hipStream_t s, const char* what = "hipStreamSynchronize") { return check(hipStreamSynchronize(s), what); }
+    // A resident-square call's outputs from its scratch buffer to the caller's host buffers, complete on return:
+    // one D2H per region, or (one_copy) one D2H of the span that covers them and a memcpy per region (proof.hip).
+    int regions_out(const OutRegions& out, const uint8_t* scratch, bool one_copy, hipStream_t s, const char* what);
     // stages enqueued since the context's work was last seen complete (for
     // attributing asynchronous device faults; see check())
     static constexpr size_t kMaxPending = 48;

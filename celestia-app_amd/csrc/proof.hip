@@ -13,15 +13,20 @@
 //   row levels      level L: [W][W >> L][96]
 //   column levels   level L >= 1: [W columns][W >> L][96] (sample.hip: column-axis proofs)
 //   RFC levels      data-root tree over the 2W roots: level l: [2W >> l][32]
-// A proof is then index arithmetic on the host (which nodes: nmt
-// buildRangeProof's maximal subtrees outside the range, RFC aunts bottom-up)
-// plus one gather launch and one copy back.
+// Share-range proofs and samples are then served by one launch each, whose
+// kernels do the index arithmetic themselves (share_proofs.hip: the one
+// producer of share-range proofs, for one range or many; sample.hip).  What is
+// left here: building the square, reading it back, and the subtree roots and
+// blob commitments, which are index arithmetic on the host plus one gather
+// launch.
 #include <algorithm>
 #include <cstring>
 #include <string>
 
 #include "../../include/cda.h"
 #include "engine.h"
+#include "out_regions.h"
+#include "resident_proof_dev.h"
 #include "sha256_dev.h"
 #include "tree_index.h"
 
@@ -51,21 +56,9 @@ __global__ __launch_bounds__(1024) void rfc_levels_kernel(uint32_t* __restrict__
 }
 
 // Copies of (src, len) pieces into one output buffer: one workgroup per piece.
-struct Piece {
-    const uint8_t* src;
-    uint64_t dst;
-    uint32_t len;
-    uint32_t kind;   // 0 raw bytes, 1 digest words -> big-endian bytes (32 B)
-};
-
-__global__ __launch_bounds__(256) void gather_kernel(const Piece* __restrict__ pieces, uint8_t* __restrict__ out) {
-    const Piece p = pieces[blockIdx.x];
-    if (p.kind == 1) {
-        if (threadIdx.x < 8)
-            reinterpret_cast<uint32_t*>(out + p.dst)[threadIdx.x] =
-                bswap32(reinterpret_cast<const uint32_t*>(p.src)[threadIdx.x]);
-        return;
-    }
+__global__ __launch_bounds__(256) void gather_kernel(const GatherPiece* __restrict__ pieces,
+                                                     uint8_t* __restrict__ out) {
+    const GatherPiece p = pieces[blockIdx.x];
     for (uint32_t i = threadIdx.x; i < p.len; i += blockDim.x) out[p.dst + i] = p.src[i];
 }
 
@@ -85,6 +78,11 @@ uint64_t ResidentSquare::level_offset(uint32_t L) const {   // bytes into `level
 
 uint64_t ResidentSquare::col_level_offset(uint32_t L) const {   // bytes into `col_levels`, L >= 1
     return cda::level_offset(2 * k, L, 1, kSlot);
+}
+
+ResidentView ResidentSquare::view() const {
+    return ResidentView{eds.as<uint8_t>(), levels.as<uint8_t>(), col_levels.as<uint8_t>(), roots_slots.as<uint8_t>(),
+                        rfc.as<uint32_t>(), k, log_w};
 }
 
 int Engine::square_create(const uint8_t* ods, uint32_t k, ResidentSquare* sq) {
@@ -156,76 +154,26 @@ int Engine::square_gather_device(ResidentSquare* sq, const std::vector<GatherPie
     hipStream_t s = stream_;
     CDA_TRY(ensure(sq->scratch, out_len ? out_len : 1, "hipMalloc"));
     if (pieces.empty()) return CDA_OK;
-    std::vector<Piece> P(pieces.size());
-    for (size_t i = 0; i < pieces.size(); i++) {
-        const GatherPiece& g = pieces[i];
-        const DevBuf* b = g.buf == GatherPiece::kEds      ? &sq->eds
-                          : g.buf == GatherPiece::kLevels ? &sq->levels
-                          : g.buf == GatherPiece::kRfc    ? &sq->rfc
-                          : g.buf == GatherPiece::kRows   ? &sq->rows
-                                                          : &sq->roots_slots;
-        P[i] = Piece{b->as<uint8_t>() + g.src, g.dst, g.len, g.buf == GatherPiece::kRfc ? 1u : 0u};
-    }
-    CDA_TRY(ensure(sq->pieces, P.size() * sizeof(Piece), "hipMalloc"));
-    CDA_TRY(h2d(sq->pieces.ptr, P.data(), P.size() * sizeof(Piece), s, "H2D pieces"));
-    hipLaunchKernelGGL(gather_kernel, dim3((uint32_t)P.size()), dim3(256), 0, s, sq->pieces.as<Piece>(),
+    CDA_TRY(ensure(sq->pieces, pieces.size() * sizeof(GatherPiece), "hipMalloc"));
+    CDA_TRY(h2d(sq->pieces.ptr, pieces.data(), pieces.size() * sizeof(GatherPiece), s, "H2D pieces"));
+    hipLaunchKernelGGL(gather_kernel, dim3((uint32_t)pieces.size()), dim3(256), 0, s, sq->pieces.as<GatherPiece>(),
                        sq->scratch.as<uint8_t>());
     CDA_TRY(launched("gather"));
-    // `P` is pageable: make sure the copy has left it before returning
+    // `pieces` is pageable: make sure the copy has left it before returning
     return sync(s);
 }
 
-// ---------------------------------------------------------------------------
-// Share inclusion proof (pkg/proof/proof.go:77-206)
-// ---------------------------------------------------------------------------
-int Engine::square_share_proof(ResidentSquare* sq, uint32_t start, uint32_t end, ShareProofOut* o) {
-    const uint32_t k = sq->k, W = 2 * k, logW = sq->log_w;
-    if (start >= end || end > k * k) return fail(CDA_ERR_INVALID, "share range out of the original square");
-    const uint32_t startRow = start / k, endRow = (end - 1) / k;
-    const uint32_t startLeaf = start % k, endLeaf = (end - 1) % k;
-    const uint32_t nrows = endRow - startRow + 1, maxn = 2 * logW, naunts = ceil_log2(2 * W);
-    // staging layout: shares | nodes [nrows][maxn][90] | roots [nrows][90] | leaf hash [nrows][32] | aunts
-    const size_t sh_b = (size_t)(end - start) * kShare;
-    const size_t nd_off = sh_b, rt_off = nd_off + (size_t)nrows * maxn * kNode;
-    const size_t lh_off = rt_off + (size_t)nrows * kNode, au_off = lh_off + (size_t)nrows * 32;
-    const size_t total = au_off + (size_t)nrows * naunts * 32;
-    std::vector<GatherPiece> pieces;
-    size_t sh_at = 0;
-    // RFC level offsets (entries) of the data-root tree over 2W items
-    std::vector<uint64_t> rfc_off(naunts + 1, 0);
-    for (uint32_t l = 0; l < naunts; l++) rfc_off[l + 1] = rfc_off[l] + ((2ull * W) >> l);
-    for (uint32_t i = 0; i < nrows; i++) {
-        const uint32_t r = startRow + i;
-        const uint32_t s0 = i == 0 ? startLeaf : 0;
-        const uint32_t e0 = (i == nrows - 1 ? endLeaf : k - 1) + 1;
-        o->nmt_start[i] = (int32_t)s0;
-        o->nmt_end[i] = (int32_t)e0;
-        pieces.push_back(GatherPiece{GatherPiece::kEds, ((uint64_t)r * W + s0) * kShare, sh_at, (e0 - s0) * kShare});
-        sh_at += (size_t)(e0 - s0) * kShare;
-        std::vector<std::pair<uint32_t, uint32_t>> nodes;
-        prove_nodes(0, W, s0, e0, nodes);
-        o->nmt_count[i] = (uint32_t)nodes.size();
-        for (size_t q = 0; q < nodes.size(); q++) {
-            const uint32_t L = nodes[q].first, p = nodes[q].second;
-            const uint64_t src = sq->level_offset(L) + ((uint64_t)r * (W >> L) + p) * kSlot;
-            pieces.push_back(GatherPiece{GatherPiece::kLevels, src, nd_off + ((size_t)i * maxn + q) * kNode, kNode});
-        }
-        pieces.push_back(GatherPiece{GatherPiece::kRows, (uint64_t)r * kNode, rt_off + (size_t)i * kNode, kNode});
-        pieces.push_back(GatherPiece{GatherPiece::kRfc, (uint64_t)r * 32, lh_off + (size_t)i * 32, 32});
-        uint32_t idx = r;   // merkle.ProofsFromByteSlices: aunts bottom-up
-        for (uint32_t l = 0; l < naunts; l++, idx >>= 1)
-            pieces.push_back(GatherPiece{GatherPiece::kRfc, (rfc_off[l] + (idx ^ 1)) * 32,
-                                         au_off + ((size_t)i * naunts + l) * 32, 32});
+int Engine::regions_out(const OutRegions& out, const uint8_t* scratch, bool one_copy, hipStream_t s,
+                        const char* what) {
+    if (!one_copy) {
+        for (const OutRegions::Region& r : out.copies()) CDA_TRY(d2h(r.host, scratch + r.off, r.bytes, s, what));
+        return sync(s);
     }
-    std::vector<uint8_t> buf(total);
-    CDA_TRY(square_gather(sq, pieces, buf.data(), total));
-    o->start_row = startRow;
-    o->end_row = endRow;
-    if (o->shares) std::memcpy(o->shares, buf.data(), sh_b);
-    if (o->nmt_nodes) std::memcpy(o->nmt_nodes, buf.data() + nd_off, (size_t)nrows * maxn * kNode);
-    if (o->row_roots) std::memcpy(o->row_roots, buf.data() + rt_off, (size_t)nrows * kNode);
-    if (o->row_leaf_hash) std::memcpy(o->row_leaf_hash, buf.data() + lh_off, (size_t)nrows * 32);
-    if (o->row_aunts) std::memcpy(o->row_aunts, buf.data() + au_off, (size_t)nrows * naunts * 32);
+    const OutRegions::Span span = out.span();
+    std::vector<uint8_t> buf(span.bytes);
+    if (span.bytes) CDA_TRY(d2h(buf.data(), scratch + span.off, span.bytes, s, what));
+    CDA_TRY(sync(s));
+    for (const OutRegions::Region& r : out.copies()) std::memcpy(r.host, buf.data() + (r.off - span.off), r.bytes);
     return CDA_OK;
 }
 
@@ -246,10 +194,10 @@ int Engine::square_subtree_root(ResidentSquare* sq, uint32_t row, const uint8_t*
     for (uint32_t i = 0; i < d; i++) pos = 2 * pos + (walk[i] ? 1u : 0u);
     const uint32_t L = logW - d;
     // the levels below the root are kept per row tree; the root itself is the row root
-    const GatherPiece piece = L == logW
-                                  ? GatherPiece{GatherPiece::kRows, (uint64_t)row * kNode, 0, kNode}
-                                  : GatherPiece{GatherPiece::kLevels,
-                                                sq->level_offset(L) + ((uint64_t)row * (W >> L) + pos) * kSlot, 0, kNode};
+    const uint8_t* src = L == logW ? sq->rows.as<uint8_t>() + (uint64_t)row * kNode
+                                   : sq->levels.as<uint8_t>() + sq->level_offset(L) +
+                                         ((uint64_t)row * (W >> L) + pos) * kSlot;
+    const GatherPiece piece{src, 0, kNode};
     CDA_TRY(square_gather(sq, {piece}, out, kNode));
     if (walk_len > logW) {   // walk(leaf, rest): the leaf is not in the cache -- Go's %v of its bytes
         std::string msg = "did not find sub tree root: [";
@@ -333,7 +281,7 @@ int Engine::square_blob_commitments(ResidentSquare* sq, const uint32_t* starts, 
                 // depth d of the ODS half of the row tree = level maxDepth - d of the full row tree
                 const uint32_t L = (uint32_t)(maxDepth - c.depth);
                 const uint64_t src = sq->level_offset(L) + ((uint64_t)r * (W >> L) + (uint32_t)c.position) * kSlot;
-                pieces.push_back(GatherPiece{GatherPiece::kLevels, src, (uint64_t)pieces.size() * kSlot, kSlot});
+                pieces.push_back(GatherPiece{sq->levels.as<uint8_t>() + src, (uint64_t)pieces.size() * kSlot, kSlot});
                 cnt++;
             }
         }

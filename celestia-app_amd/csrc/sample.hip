@@ -25,7 +25,10 @@
 // (16-byte loads, proof order) into LDS and then writes the packed bytes with
 // one aligned 4-byte store per lane, consecutive lanes on consecutive words
 // (256 B per wave instruction), the at most three bytes at either end of a
-// region singly.  Shares and digests are aligned and go out directly.
+// region singly.  Shares and digests are aligned and go out directly.  The
+// staging, the merkle proof of the root and the view of the square are the ones
+// share_proofs.hip uses (resident_proof_dev.h); the scratch layout and the
+// copies back are out_regions.h's.
 // Every index the kernel uses was validated on the host
 // (Engine::square_sample_proofs).
 #include <cstring>
@@ -34,7 +37,8 @@
 
 #include "../../include/cda.h"
 #include "engine.h"
-#include "packed_store_dev.h"
+#include "out_regions.h"
+#include "resident_proof_dev.h"
 #include "sha256_dev.h"
 #include "tree_index.h"
 
@@ -43,17 +47,12 @@ namespace cda {
 namespace {
 
 constexpr uint32_t kSampleWaves = 4;      // samples per workgroup
-constexpr uint32_t kSampleMaxD = 11;      // log2(2 * 1024)
-constexpr uint32_t kSampleSlots = kSampleMaxD + 2;   // proof nodes, the axis root, the namespace
+constexpr uint32_t kSampleSlots = kProofMaxD + 2;   // proof nodes, the axis root, the namespace
 
 struct SampleArgs {
+    ResidentView sq;
     const uint32_t* coords;     // n words: row | col << 12 | axis << 24
-    uint32_t n, k, log_w;
-    const uint8_t* eds;         // [W][W][512]
-    const uint8_t* levels;      // row levels, level 0 = the leaf slots
-    const uint8_t* col_levels;  // column levels 1..
-    const uint8_t* root_slots;  // [2W][96]: row roots, then column roots
-    const uint32_t* rfc;        // RFC-6962 levels of the data-root tree, state words
+    uint32_t n;
     uint8_t* shares;            // any output may be NULL
     uint8_t* namespaces;
     uint8_t* nodes;
@@ -63,11 +62,12 @@ struct SampleArgs {
 };
 
 __global__ __launch_bounds__(64 * kSampleWaves) void sample_kernel(const SampleArgs a) {
-    __shared__ uint4 stage[kSampleWaves][kSampleSlots * (kSlot / 16)];
+    __shared__ uint4 stage[kSampleWaves][stage_row(kSampleSlots)];
     const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const uint32_t i = blockIdx.x * kSampleWaves + wave;
     const bool live = i < a.n;   // uniform over the wave; no early return: the workgroup meets at the barrier
-    const uint32_t W = 2 * a.k, D = a.log_w, A = D + 1;
+    const ResidentView& v = a.sq;
+    const uint32_t W = 2 * v.k, D = v.log_w, A = D + 1;
     uint32_t row = 0, col = 0, axis = 0;
     if (live) {
         const uint32_t c = a.coords[i];
@@ -82,46 +82,27 @@ __global__ __launch_bounds__(64 * kSampleWaves) void sample_kernel(const SampleA
     if (live) {
         // the share: 32 lanes x 16 bytes; its first two words also give the Q0 namespace
         uint4 sh = make_uint4(0, 0, 0, 0);
-        if (lane < 32) sh = reinterpret_cast<const uint4*>(a.eds + cell * kShare)[lane];
+        if (lane < 32) sh = reinterpret_cast<const uint4*>(v.eds + cell * kShare)[lane];
         if (a.shares && lane < 32) reinterpret_cast<uint4*>(a.shares + (uint64_t)i * kShare)[lane] = sh;
         if (lane < 2) {
-            const bool q0 = row < a.k && col < a.k;   // else ParitySharesNamespace: 29 bytes of 0xFF
-            st[(D + 1) * (kSlot / 16) + lane] = q0 ? sh : make_uint4(~0u, ~0u, ~0u, ~0u);
+            const bool q0 = row < v.k && col < v.k;   // else ParitySharesNamespace: 29 bytes of 0xFF
+            st[stage_row(D + 1) + lane] = q0 ? sh : make_uint4(~0u, ~0u, ~0u, ~0u);
         }
-        // the D siblings in proof order, then the axis root: six 16-byte loads per slot
-        for (uint32_t q = lane; q < (D + 1) * (kSlot / 16); q += 64) {
-            const uint32_t L = q / (kSlot / 16), part = q % (kSlot / 16);
+        // the D siblings in proof order, then the axis root
+        stage_slots(st, D + 1, lane, [&](uint32_t L) {
+            if (L == D) return StagedSlot{v.root_slots + (uint64_t)(axis * W + tree) * kSlot, D};
+            const uint32_t sib = (p >> L) ^ 1u;
             const uint8_t* src;
-            uint32_t j;
-            if (L == D) {
-                src = a.root_slots + (uint64_t)(axis * W + tree) * kSlot;
-                j = D;
-            } else {
-                const uint32_t sib = (p >> L) ^ 1u;
-                if (L == 0)   // the leaf level: shared by both axes, a column reads it with stride W
-                    src = a.levels + (axis ? (uint64_t)sib * W + tree : (uint64_t)tree * W + sib) * kSlot;
-                else if (axis)
-                    src = a.col_levels + level_offset(W, L, 1, kSlot) + ((uint64_t)tree * (W >> L) + sib) * kSlot;
-                else
-                    src = a.levels + level_offset(W, L, 0, kSlot) + ((uint64_t)tree * (W >> L) + sib) * kSlot;
-                j = ((p >> L) & 1u) ? (uint32_t)__popc(p >> (L + 1))
-                                    : (uint32_t)__popc(p) + L - (uint32_t)__popc(p & ((1u << L) - 1u));
-            }
-            st[j * (kSlot / 16) + part] = reinterpret_cast<const uint4*>(src)[part];
-        }
-        // leaf hash and aunts: state words out as big-endian bytes, one word per lane
-        const uint32_t idx = axis * W + tree, T = 2 * W;   // Index among the Total = 4k roots
-        for (uint32_t q = lane; q < (A + 1) * 8; q += 64) {
-            const uint32_t item = q / 8, word = q % 8;
-            if (item == 0) {
-                if (a.leaf_hash)
-                    reinterpret_cast<uint32_t*>(a.leaf_hash + (uint64_t)i * 32)[word] = bswap32(a.rfc[(uint64_t)idx * 8 + word]);
-            } else if (a.aunts) {
-                const uint32_t l = item - 1;
-                const uint64_t entry = (uint64_t)(2 * T - ((2 * T) >> l)) + ((idx >> l) ^ 1u);
-                reinterpret_cast<uint32_t*>(a.aunts + ((uint64_t)i * A + l) * 32)[word] = bswap32(a.rfc[entry * 8 + word]);
-            }
-        }
+            if (L == 0)   // the leaf level: shared by both axes, a column reads it with stride W
+                src = v.levels + (axis ? (uint64_t)sib * W + tree : (uint64_t)tree * W + sib) * kSlot;
+            else if (axis)
+                src = v.col_levels + level_offset(W, L, 1, kSlot) + ((uint64_t)tree * (W >> L) + sib) * kSlot;
+            else
+                src = v.levels + level_offset(W, L, 0, kSlot) + ((uint64_t)tree * (W >> L) + sib) * kSlot;
+            return StagedSlot{src, ((p >> L) & 1u) ? (uint32_t)__popc(p >> (L + 1))
+                                                   : (uint32_t)__popc(p) + L - (uint32_t)__popc(p & ((1u << L) - 1u))};
+        });
+        store_root_proof(v.rfc, W, A, axis * W + tree, i, a.leaf_hash, a.aunts, lane);   // Index among the 4k roots
     }
     __syncthreads();
     if (!live) return;
@@ -155,63 +136,33 @@ int Engine::square_sample_proofs(ResidentSquare* sq, const uint32_t* rows, const
     if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
     std::vector<uint32_t> packed(n);
     for (uint32_t i = 0; i < n; i++) packed[i] = rows[i] | (cols[i] << 12) | ((axes ? axes[i] : 0u) << 24);
-    // scratch: the packed coordinates, then one struct-of-arrays region per requested output, each at a
-    // 16-byte boundary
-    struct Region {
-        uint8_t* host;
-        size_t bytes, off;
-    };
-    size_t total = ((size_t)n * 4 + 15) & ~(size_t)15;
-    auto region = [&](uint8_t* host, size_t bytes) {
-        Region r{host, host ? bytes : 0, total};
-        total += (r.bytes + 15) & ~(size_t)15;
-        return r;
-    };
-    const Region r_sh = region(o.shares, (size_t)n * kShare), r_ns = region(o.namespaces, (size_t)n * kNs),
-                 r_nd = region(o.nmt_nodes, (size_t)n * D * kNode), r_rt = region(o.axis_roots, (size_t)n * kNode),
-                 r_lh = region(o.leaf_hash, (size_t)n * 32), r_au = region(o.aunts, (size_t)n * A * 32);
+    // scratch: the packed coordinates, then one struct-of-arrays region per requested output
+    OutRegions out((size_t)n * 4);
+    const auto r_sh = out.add(o.shares, (size_t)n * kShare), r_ns = out.add(o.namespaces, (size_t)n * kNs),
+               r_nd = out.add(o.nmt_nodes, (size_t)n * D * kNode), r_rt = out.add(o.axis_roots, (size_t)n * kNode),
+               r_lh = out.add(o.leaf_hash, (size_t)n * 32), r_au = out.add(o.aunts, (size_t)n * A * 32);
     hipStream_t s = stream_;
-    CDA_TRY(ensure(sq->scratch, total, "hipMalloc"));
+    CDA_TRY(ensure(sq->scratch, out.total(), "hipMalloc"));
     uint8_t* scr = sq->scratch.as<uint8_t>();
     CDA_TRY(h2d(scr, packed.data(), (size_t)n * 4, s, "H2D samples"));
-    auto dev = [&](const Region& r) -> uint8_t* { return r.host ? scr + r.off : nullptr; };
-    SampleArgs a{};
-    a.coords = reinterpret_cast<const uint32_t*>(scr);
-    a.n = n;
-    a.k = k;
-    a.log_w = D;
-    a.eds = sq->eds.as<uint8_t>();
-    a.levels = sq->levels.as<uint8_t>();
-    a.col_levels = sq->col_levels.as<uint8_t>();
-    a.root_slots = sq->roots_slots.as<uint8_t>();
-    a.rfc = sq->rfc.as<uint32_t>();
-    a.shares = dev(r_sh);
-    a.namespaces = dev(r_ns);
-    a.nodes = dev(r_nd);
-    a.roots = dev(r_rt);
-    a.leaf_hash = dev(r_lh);
-    a.aunts = dev(r_au);
+    const SampleArgs a{sq->view(), reinterpret_cast<const uint32_t*>(scr), n, r_sh.dev(scr), r_ns.dev(scr),
+                       r_nd.dev(scr), r_rt.dev(scr), r_lh.dev(scr), r_au.dev(scr)};
     hipLaunchKernelGGL(sample_kernel, dim3((n + kSampleWaves - 1) / kSampleWaves), dim3(64 * kSampleWaves), 0, s, a);
     CDA_TRY(launched("sample proofs"));
-    for (const Region* r : {&r_sh, &r_ns, &r_nd, &r_rt, &r_lh, &r_au})
-        if (r->bytes) CDA_TRY(d2h(r->host, scr + r->off, r->bytes, s, "D2H samples"));
     // `packed` is pageable and the outputs are the caller's: complete before returning
-    return sync(s);
+    return regions_out(out, scr, false, s, "D2H samples");
 }
 
 int Engine::sample_proofs_verify(uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
                                  const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,
                                  const uint8_t* nmt_nodes, const uint8_t* axis_roots, const uint8_t* leaf_hash,
                                  const uint8_t* aunts, uint8_t* verdict) {
-    if (k == 0 || (k & (k - 1)) || k > 1024)
+    if (!is_pow2(k) || k > 1024)
         return fail(CDA_ERR_INVALID, "square width must be a power of two <= 1024");
     if (n == 0) return CDA_OK;
     if (!data_roots || !rows || !cols || !shares || !nmt_nodes || !axis_roots || !leaf_hash || !aunts || !verdict)
         return fail(CDA_ERR_INVALID, "null buffer");
-    const uint32_t W = 2 * k;
-    uint32_t D = 0;
-    while ((1u << D) < W) D++;
-    const uint32_t A = D + 1;
+    const uint32_t W = 2 * k, D = ceil_log2(W), A = D + 1;
     const std::string bad = check_coords(rows, cols, axes, n, W);
     if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
     // Everything a prover could lie about is derived here from (row, col, axis): the leaf namespace, the

@@ -1,20 +1,23 @@
-// share_proofs.hip -- share-inclusion proofs of many ranges of a resident
-// square in ONE launch (proof.NewShareInclusionProofFromEDS, pkg/proof/
-// proof.go:77-145, for a batch of ranges), laid out as the flat batch that
-// Engine::share_proofs_verify takes (cda_share_proof_batch).
+// share_proofs.hip -- the one producer of share-inclusion proofs of a resident
+// square (proof.NewShareInclusionProofFromEDS, pkg/proof/proof.go:77-145):
+// any number of ranges in ONE launch, laid out as the flat batch that
+// Engine::share_proofs_verify takes (cda_share_proof_batch), and the
+// single-range call (cda_square_share_proof) as the same plan, table and
+// kernel with n = 1 and its own layout of the nodes.
 //
 // Proof shape.  A range covers one segment per row (share_proofs_plan.h).  The
 // row trees are perfect trees of W = 2k leaves, so the nodes of nmt
 // ProveRange(s0, e0) have the closed form of tree_index.h (range_proof_count /
 // range_proof_node): the kernel derives every source address from the segment
 // table, that closed form and level_offset.  The merkle proof of the row root
-// among rowRoots || colRoots is the one of sample.hip with Index = row.
+// among rowRoots || colRoots is the one of sample.hip with Index = row
+// (store_root_proof, resident_proof_dev.h).
 //
 // Mapping.  Two kinds of workgroup in the one launch, four wavefronts each.
 //   Proof workgroups: one wavefront per segment.  The nodes and the row root
-//   are read as six 16-byte loads per 96-byte slot into LDS in proof order and
-//   written packed (store_packed); the leaf hash and the aunts leave as
-//   big-endian words, one word per lane.  The wave of a proof's first segment
+//   are read as six 16-byte loads per 96-byte slot into LDS in proof order
+//   (stage_slots) and written packed (store_packed); the leaf hash and the
+//   aunts leave as big-endian words, one word per lane.  The wave of a proof's first segment
 //   also writes the proof's namespace.
 //   Share workgroups: one wavefront per unit of at most kUnitShares shares of
 //   one segment (8 KiB), found by a binary search of the table's unit prefix
@@ -33,7 +36,8 @@
 
 #include "../../include/cda.h"
 #include "engine.h"
-#include "packed_store_dev.h"
+#include "out_regions.h"
+#include "resident_proof_dev.h"
 #include "sha256_dev.h"
 #include "share_proofs_plan.h"
 #include "tree_index.h"
@@ -43,9 +47,11 @@ namespace cda {
 namespace {
 
 constexpr uint32_t kProofWaves = 4;        // segments, or share units, per workgroup
-constexpr uint32_t kProofMaxD = 11;        // log2(2 * 1024)
 constexpr uint32_t kProofSlots = 2 * kProofMaxD + 2;   // proof nodes, the row root, the namespace
 constexpr uint32_t kUnitShares = 16;       // shares one wave copies
+// The single-range call returns outputs of up to this many bytes in one copy (regions_out): measured against one
+// copy per output, it is faster up to 1 MiB of shares and slower from 2 MiB (profiles/resident_proof_refactor.txt).
+constexpr size_t kOneCopyBytes = 3 << 19;
 
 // One segment, as uploaded: 32 bytes.
 struct SegEntry {
@@ -60,12 +66,9 @@ struct SegEntry {
 static_assert(sizeof(SegEntry) == 32);
 
 struct ShareProofsArgs {
+    ResidentView sq;
     const SegEntry* segs;
-    uint32_t n_segs, n_units, proof_blocks, k, log_w;
-    const uint8_t* eds;         // [W][W][512]
-    const uint8_t* levels;      // row levels, level 0 = the leaf slots
-    const uint8_t* root_slots;  // [2W][96]: row roots, then column roots
-    const uint32_t* rfc;        // RFC-6962 levels of the data-root tree, state words
+    uint32_t n_segs, n_units, proof_blocks;
     uint8_t* nodes;             // any output may be NULL
     uint8_t* row_roots;
     uint8_t* leaf_hash;
@@ -81,11 +84,12 @@ __device__ __forceinline__ SegEntry load_seg(const SegEntry* p) {
 }
 
 // One wavefront per segment; every wave of the workgroup reaches the barrier.
-__device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*stage)[kProofSlots * (kSlot / 16)]) {
+__device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*stage)[stage_row(kProofSlots)]) {
     const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const uint32_t g = blockIdx.x * kProofWaves + wave;
     const bool live = g < a.n_segs;   // uniform over the wave
-    const uint32_t W = 2 * a.k, D = a.log_w, A = D + 1;
+    const ResidentView& v = a.sq;
+    const uint32_t W = 2 * v.k, D = v.log_w, A = D + 1;
     SegEntry e{};
     if (live) e = load_seg(a.segs + g);
     const uint32_t row = e.row, s0 = e.range & 0xFFFFu, e0 = live ? e.range >> 16 : 1u;
@@ -93,35 +97,17 @@ __device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*sta
     const bool first = live && e.first_cell == row * W + s0;   // the proof's first segment
     uint4* st = stage[wave];
     if (live) {
-        // the nodes in proof order, then the row root: six 16-byte loads per slot
-        for (uint32_t q = lane; q < (cnt + 1) * (kSlot / 16); q += 64) {
-            const uint32_t j = q / (kSlot / 16), part = q % (kSlot / 16);
-            const uint8_t* src;
-            if (j == cnt) {
-                src = a.root_slots + (uint64_t)row * kSlot;
-            } else {
-                const TreeNode nd = range_proof_node(D, s0, e0, j);
-                src = a.levels + level_offset(W, nd.level, 0, kSlot) +
-                      ((uint64_t)row * (W >> nd.level) + nd.index) * kSlot;
-            }
-            st[q] = reinterpret_cast<const uint4*>(src)[part];
-        }
+        // the nodes in proof order, then the row root
+        stage_slots(st, cnt + 1, lane, [&](uint32_t j) {
+            if (j == cnt) return StagedSlot{v.root_slots + (uint64_t)row * kSlot, j};
+            const TreeNode nd = range_proof_node(D, s0, e0, j);
+            return StagedSlot{v.levels + level_offset(W, nd.level, 0, kSlot) +
+                                  ((uint64_t)row * (W >> nd.level) + nd.index) * kSlot, j};
+        });
         // the namespace of the proof's first share
         if (first && lane < 2)
-            st[(cnt + 1) * (kSlot / 16) + lane] = reinterpret_cast<const uint4*>(a.eds + (uint64_t)e.first_cell * kShare)[lane];
-        // leaf hash and aunts: state words out as big-endian bytes, one word per lane
-        const uint32_t idx = row, T = 2 * W;   // Index among the Total = 4k roots
-        for (uint32_t q = lane; q < (A + 1) * 8; q += 64) {
-            const uint32_t item = q / 8, word = q % 8;
-            if (item == 0) {
-                if (a.leaf_hash)
-                    reinterpret_cast<uint32_t*>(a.leaf_hash + (uint64_t)g * 32)[word] = bswap32(a.rfc[(uint64_t)idx * 8 + word]);
-            } else if (a.aunts) {
-                const uint32_t l = item - 1;
-                const uint64_t entry = (uint64_t)(2 * T - ((2 * T) >> l)) + ((idx >> l) ^ 1u);
-                reinterpret_cast<uint32_t*>(a.aunts + ((uint64_t)g * A + l) * 32)[word] = bswap32(a.rfc[entry * 8 + word]);
-            }
-        }
+            st[stage_row(cnt + 1) + lane] = reinterpret_cast<const uint4*>(v.eds + (uint64_t)e.first_cell * kShare)[lane];
+        store_root_proof(v.rfc, W, A, row, g, a.leaf_hash, a.aunts, lane);   // Index = row among the 4k roots
     }
     __syncthreads();
     if (!live) return;
@@ -144,17 +130,17 @@ __device__ __forceinline__ void share_part(const ShareProofsArgs& a) {
         else hi = mid - 1;
     }
     const SegEntry e = load_seg(a.segs + lo);
-    const uint32_t W = 2 * a.k, s0 = e.range & 0xFFFFu, e0 = e.range >> 16;
+    const uint32_t W = 2 * a.sq.k, s0 = e.range & 0xFFFFu, e0 = e.range >> 16;
     const uint32_t at = (u - e.unit_off) * kUnitShares;   // first share of the unit within the segment
     const uint32_t cnt = min(kUnitShares, e0 - s0 - at);
-    const uint4* src = reinterpret_cast<const uint4*>(a.eds + ((uint64_t)e.row * W + s0 + at) * kShare);
+    const uint4* src = reinterpret_cast<const uint4*>(a.sq.eds + ((uint64_t)e.row * W + s0 + at) * kShare);
     uint4* dst = a.shares ? reinterpret_cast<uint4*>(a.shares + (e.share_off + at) * kShare) : nullptr;
     constexpr uint32_t V = kShare / 16;   // 16-byte pieces per share
     const uint32_t part = lane % V;
     // the proof's first namespace: bytes 0..28 are pieces 0 and 1 without the last three bytes
     const bool ns_lane = a.flags && part < 2;
     uint4 ref = make_uint4(0, 0, 0, 0);
-    if (ns_lane) ref = reinterpret_cast<const uint4*>(a.eds + (uint64_t)e.first_cell * kShare)[part];
+    if (ns_lane) ref = reinterpret_cast<const uint4*>(a.sq.eds + (uint64_t)e.first_cell * kShare)[part];
     const uint32_t last_mask = part == 1 ? 0x000000FFu : 0xFFFFFFFFu;
     bool differs = false;
     constexpr uint32_t kIters = kUnitShares * V / 64;   // pieces per lane: all loads in flight, then the stores
@@ -181,16 +167,27 @@ __device__ __forceinline__ void share_part(const ShareProofsArgs& a) {
 }
 
 __global__ __launch_bounds__(64 * kProofWaves) void share_proofs_kernel(const ShareProofsArgs a) {
-    __shared__ uint4 stage[kProofWaves][kProofSlots * (kSlot / 16)];
+    __shared__ uint4 stage[kProofWaves][stage_row(kProofSlots)];
     if (blockIdx.x < a.proof_blocks) proof_part(a, stage);   // uniform over the workgroup
     else share_part(a);
 }
 
 }  // namespace
 
+// One range per call (cda_square_share_proof): the batch with n = 1, the nodes of row i in their documented
+// place, slot i * M of nmt_nodes.  A proof of a few shares is a few KiB over five buffers, where every pageable
+// copy costs more than its bytes: small outputs come back in one copy (kOneCopyBytes).
+int Engine::square_share_proof(ResidentSquare* sq, uint32_t start, uint32_t end, const cda_share_proofs_out& o,
+                               uint32_t* nmt_count) {
+    if (start >= end || end > sq->k * sq->k) return fail(CDA_ERR_INVALID, "share range out of the original square");
+    return square_share_proofs(sq, &start, &end, 1, o, nmt_count, kOneCopyBytes);
+}
+
+// nmt_count == NULL: the nodes packed, node_off beside them.  Else segment g's nodes start at slot g * M,
+// M = 2 log2 W, and nmt_count[g] of them are valid.  one_copy_max: outputs up to this size return in one copy.
 int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, const uint32_t* ends, uint32_t n,
-                                const cda_share_proofs_out& o) {
-    const uint32_t k = sq->k, W = 2 * k, D = sq->log_w, A = D + 1;
+                                const cda_share_proofs_out& o, uint32_t* nmt_count, size_t one_copy_max) {
+    const uint32_t k = sq->k, W = 2 * k, D = sq->log_w, A = D + 1, M = 2 * D;
     ShareProofsPlan plan;
     const std::string bad = share_proofs_plan(k, starts, ends, n, &plan);
     if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
@@ -212,12 +209,15 @@ int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, cons
     for (uint32_t i = 0; i < n; i++) {
         const uint32_t first_cell = (starts[i] / k) * W + starts[i] % k;
         for_each_segment(k, i, starts[i], ends[i], [&](const ShareProofSegment& sg) {
-            segs[g] = SegEntry{sg.row, sg.s0 | (sg.e0 << 16), node_at, unit_at, share_at, i, first_cell};
+            const uint32_t count = range_proof_count(D, sg.s0, sg.e0);
+            segs[g] = SegEntry{sg.row, sg.s0 | (sg.e0 << 16), nmt_count ? g * M : node_at, unit_at, share_at, i,
+                               first_cell};
+            if (nmt_count) nmt_count[g] = count;
             if (o.nmt_start) o.nmt_start[g] = (int32_t)sg.s0;
             if (o.nmt_end) o.nmt_end[g] = (int32_t)sg.e0;
             if (o.rfc_total) o.rfc_total[g] = 2ll * W;
             if (o.rfc_index) o.rfc_index[g] = sg.row;
-            node_at += range_proof_count(D, sg.s0, sg.e0);
+            node_at += count;
             unit_at += (sg.e0 - sg.s0 + kUnitShares - 1) / kUnitShares;
             share_at += sg.e0 - sg.s0;
             g++;
@@ -228,43 +228,20 @@ int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, cons
         if (o.start_row) o.start_row[i] = starts[i] / k;
         if (o.end_row) o.end_row[i] = (ends[i] - 1) / k;
     }
-    // scratch: the upload, then one region per requested output, each at a 16-byte boundary
-    struct Region {
-        uint8_t* host;
-        size_t bytes, off;
-    };
-    const size_t table_bytes = (size_t)S * sizeof(SegEntry);
-    size_t total = (up.size() * 4 + 15) & ~(size_t)15;
-    auto region = [&](uint8_t* host, size_t bytes) {
-        Region r{host, host ? bytes : 0, total};
-        total += (r.bytes + 15) & ~(size_t)15;
-        return r;
-    };
-    const Region r_nd = region(o.nodes, (size_t)plan.n_nodes * kNode), r_rt = region(o.row_roots, (size_t)S * kNode),
-                 r_lh = region(o.rfc_leaf_hash, (size_t)S * 32), r_au = region(o.aunts, (size_t)plan.n_aunts * 32),
-                 r_sh = region(o.shares, (size_t)plan.n_shares * kShare), r_ns = region(o.namespaces, (size_t)n * kNs);
-    const Region r_fl{o.one_namespace, o.one_namespace ? (size_t)n : 0, table_bytes};   // inside the upload
+    // scratch: the upload, then one region per requested output; the flags lie inside the upload
+    OutRegions out(up.size() * 4);
+    const size_t node_slots = nmt_count ? (size_t)S * M : plan.n_nodes;
+    const auto r_nd = out.add(o.nodes, node_slots * kNode), r_rt = out.add(o.row_roots, (size_t)S * kNode),
+               r_lh = out.add(o.rfc_leaf_hash, (size_t)S * 32), r_au = out.add(o.aunts, (size_t)plan.n_aunts * 32),
+               r_sh = out.add(o.shares, (size_t)plan.n_shares * kShare), r_ns = out.add(o.namespaces, (size_t)n * kNs),
+               r_fl = out.add_at(o.one_namespace, (size_t)S * sizeof(SegEntry), n);
     hipStream_t s = stream_;
-    CDA_TRY(ensure(sq->scratch, total, "hipMalloc"));
+    CDA_TRY(ensure(sq->scratch, out.total(), "hipMalloc"));
     uint8_t* scr = sq->scratch.as<uint8_t>();
     CDA_TRY(h2d(scr, up.data(), up.size() * 4, s, "H2D share proofs"));
-    auto dev = [&](const Region& r) -> uint8_t* { return r.host ? scr + r.off : nullptr; };
-    ShareProofsArgs a{};
-    a.segs = reinterpret_cast<const SegEntry*>(scr);
-    a.n_segs = S;
-    a.k = k;
-    a.log_w = D;
-    a.eds = sq->eds.as<uint8_t>();
-    a.levels = sq->levels.as<uint8_t>();
-    a.root_slots = sq->roots_slots.as<uint8_t>();
-    a.rfc = sq->rfc.as<uint32_t>();
-    a.nodes = dev(r_nd);
-    a.row_roots = dev(r_rt);
-    a.leaf_hash = dev(r_lh);
-    a.aunts = dev(r_au);
-    a.shares = dev(r_sh);
-    a.namespaces = dev(r_ns);
-    a.flags = reinterpret_cast<uint32_t*>(dev(r_fl));
+    ShareProofsArgs a{sq->view(), reinterpret_cast<const SegEntry*>(scr), S, 0, 0, r_nd.dev(scr), r_rt.dev(scr),
+                      r_lh.dev(scr), r_au.dev(scr), r_sh.dev(scr), r_ns.dev(scr),
+                      reinterpret_cast<uint32_t*>(r_fl.dev(scr))};
     const bool proof_half = a.nodes || a.row_roots || a.leaf_hash || a.aunts || a.namespaces;
     a.proof_blocks = proof_half ? (S + kProofWaves - 1) / kProofWaves : 0;
     a.n_units = a.shares || a.flags ? unit_at : 0;
@@ -273,10 +250,8 @@ int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, cons
         hipLaunchKernelGGL(share_proofs_kernel, dim3(blocks), dim3(64 * kProofWaves), 0, s, a);
         CDA_TRY(launched("share proofs"));
     }
-    for (const Region* r : {&r_nd, &r_rt, &r_lh, &r_au, &r_sh, &r_ns, &r_fl})
-        if (r->bytes) CDA_TRY(d2h(r->host, scr + r->off, r->bytes, s, "D2H share proofs"));
     // `up` is pageable and the outputs are the caller's: complete before returning
-    return sync(s);
+    return regions_out(out, scr, out.span().bytes <= one_copy_max, s, "D2H share proofs");
 }
 
 }  // namespace cda

@@ -418,7 +418,7 @@ int cda_blob_commitments_device(cda_ctx *ctx, const uint8_t *namespaces, const u
  * (SURVEY.md 8(f) row 3).  cda_square_create extends one ODS and keeps in HBM
  * the EDS, every level of every row tree (the reference's
  * EDSSubTreeRootCacher, pkg/inclusion/nmt_caching.go:80-124) and all levels
- * of the data-root tree, so proofs are index arithmetic plus one gather.
+ * of the data-root tree, so a proof is index arithmetic and one launch.
  * On CDA_ERR_PUSH_ORDER the handle is still created (the EDS exists). */
 typedef struct cda_square cda_square;
 int cda_square_create(cda_ctx *ctx, const uint8_t *ods, uint32_t n_shares, cda_square **out);
