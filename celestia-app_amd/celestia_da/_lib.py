@@ -70,7 +70,11 @@ EXPORTED = (
     "cda_extend_dah_multi", "cda_split_layout", "cda_split_offsets", "cda_extend_dah_batch_ex",
     "cda_share_proofs_verify", "cda_square_sample_proofs", "cda_sample_proofs_verify",
     "cda_square_share_proofs_plan", "cda_square_share_proofs", "cda_square_tx_share_ranges",
+    "cda_square_namespace_plan", "cda_square_namespace_proofs", "cda_namespace_proofs_verify",
 )
+# cda_namespace_proof_batch kinds (include/cda.h)
+CDA_NAMESPACE_INCLUSION = 1
+CDA_NAMESPACE_ABSENCE = 2
 # cda_square_sample_proofs axes (include/cda.h)
 CDA_AXIS_ROW = 0
 CDA_AXIS_COL = 1
@@ -145,6 +149,31 @@ class ShareProofsOut(C.Structure):
                 ("nodes", _u8p), ("row_roots", _u8p), ("rfc_total", _i64p), ("rfc_index", _i64p),
                 ("rfc_leaf_hash", _u8p), ("aunt_off", _u32p), ("aunts", _u8p), ("shares", _u8p),
                 ("namespaces", _u8p), ("start_row", _u32p), ("end_row", _u32p), ("one_namespace", _u8p)]
+
+
+class NamespacePlanT(C.Structure):
+    """cda_namespace_plan_t (include/cda.h)."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_segments", "n_nodes", "n_shares")]
+
+
+class NamespaceProofsOut(C.Structure):
+    """cda_namespace_proofs_out (include/cda.h)."""
+    _u8p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    _i32p, _u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    _fields_ = [("seg_off", _u32p), ("row", _u32p), ("kind", _u8p), ("nmt_start", _i32p), ("nmt_end", _i32p),
+                ("node_off", _u32p), ("nodes", _u8p), ("share_off", _u64p), ("shares", _u8p),
+                ("absence_leaf", _u8p)]
+
+
+class NamespaceProofBatch(C.Structure):
+    """cda_namespace_proof_batch (include/cda.h): NamespaceProofsOut's arrays, read-only, with the queries and
+    the counts."""
+    _u8p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    _i32p, _u64p = C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
+    _fields_ = [("n_queries", C.c_uint32), ("namespaces", _u8p), ("seg_off", _u32p), ("row", _u32p), ("kind", _u8p),
+                ("nmt_start", _i32p), ("nmt_end", _i32p), ("node_off", _u32p), ("nodes", _u8p),
+                ("n_nodes", C.c_uint32), ("share_off", _u64p), ("shares", _u8p), ("n_shares", C.c_uint64),
+                ("absence_leaf", _u8p)]
 
 
 _lib = None
@@ -235,6 +264,9 @@ def load(path: str | None = None):
                                                u8p, u8p, u8p]
         L.cda_square_share_proofs_plan.argtypes = [C.c_uint32, u32p, u32p, C.c_uint32, C.POINTER(ShareProofsPlanT)]
         L.cda_square_share_proofs.argtypes = [vp, u32p, u32p, C.c_uint32, C.POINTER(ShareProofsOut)]
+        L.cda_square_namespace_plan.argtypes = [vp, u8p, C.c_uint32, C.POINTER(NamespacePlanT)]
+        L.cda_square_namespace_proofs.argtypes = [vp, u8p, C.c_uint32, C.POINTER(NamespaceProofsOut)]
+        L.cda_namespace_proofs_verify.argtypes = [ctxp, C.c_uint32, u8p, C.POINTER(NamespaceProofBatch), u8p]
         L.cda_comm_unique_id.argtypes = [u8p]
         L.cda_comm_init.argtypes = [ctxp, C.c_int, C.c_int, u8p]
         L.cda_comm_destroy.argtypes = [ctxp]

@@ -235,6 +235,14 @@ class ResidentSquare:
         from . import sampling
         return sampling.sample_proofs(self, coords, out)
 
+    def namespace_proofs(self, namespaces, out=None):
+        """All shares of every 29-byte namespace of `namespaces` with nmt
+        ProveNamespace's proofs, absence proofs included, the rows chosen as
+        GetSharesByNamespace chooses them (cda_square_namespace_plan /
+        _proofs): a namespace.NamespaceProofsBatch."""
+        from . import namespace
+        return namespace.namespace_proofs(self, namespaces, out)
+
     def blob_commitments(self, starts, share_lens, subtree_root_threshold: int = 64):
         """inclusion.GetCommitment for each (start, share_len)."""
         n = len(starts)

@@ -636,6 +636,28 @@ int cda_square_share_proofs(cda_square* sq, const uint32_t* starts, const uint32
     });
 }
 
+int cda_square_namespace_plan(cda_square* sq, const uint8_t* namespaces, uint32_t n, cda_namespace_plan_t* out) {
+    if (!sq) return CDA_ERR_INVALID;
+    return guarded(sq->ctx, [&](cda::Engine& e) -> int {
+        if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.square_namespace_plan(&sq->sq, namespaces, n, out);
+    });
+}
+
+int cda_square_namespace_proofs(cda_square* sq, const uint8_t* namespaces, uint32_t n,
+                                const cda_namespace_proofs_out* out) {
+    if (!sq) return CDA_ERR_INVALID;
+    return guarded(sq->ctx, [&](cda::Engine& e) -> int {
+        if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.square_namespace_proofs(&sq->sq, namespaces, n, *out);
+    });
+}
+
+int cda_namespace_proofs_verify(cda_ctx* ctx, uint32_t k, const uint8_t* row_roots,
+                                const cda_namespace_proof_batch* b, uint8_t* verdict) {
+    return guarded(ctx, [&](cda::Engine& e) -> int { return e.namespace_proofs_verify(k, row_roots, b, verdict); });
+}
+
 int cda_sample_proofs_verify(cda_ctx* ctx, uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
                              const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,
                              const uint8_t* nmt_nodes, const uint8_t* axis_roots, const uint8_t* leaf_hash,

@@ -17,9 +17,13 @@
 
 struct cda_share_proof_batch;   // include/cda.h
 struct cda_share_proofs_out;
+struct cda_namespace_plan_t;
+struct cda_namespace_proofs_out;
+struct cda_namespace_proof_batch;
 namespace cda {
 class OutRegions;      // out_regions.h
 struct ResidentView;   // resident_proof_dev.h
+struct SegmentEmit;    // segment_table.h
 }
 
 // The one early-return form of the host code: a non-zero CDA_* code leaves the function.
@@ -295,6 +299,17 @@ class Engine {
     // row, nmt_count[i] of row i's valid.
     int square_share_proof(ResidentSquare* sq, uint32_t start, uint32_t end, const cda_share_proofs_out& out,
                            uint32_t* nmt_count);
+    // What both producers of a segment table end in (share_proofs.hip): the table up, the proof kernel's one
+    // launch, the requested outputs back; complete on return.
+    int emit_segments(ResidentSquare* sq, const SegmentEmit& em);
+    // All shares of n namespaces with nmt ProveNamespace's proofs, absence proofs included (namespace_proofs.hip):
+    // one search launch whose (query, row) words come back, the host plan (namespace_proofs_plan.h), and for the
+    // proofs emit_segments.  A square whose push order failed answers CDA_ERR_PUSH_ORDER.
+    int square_namespace_search(ResidentSquare* sq, const uint8_t* namespaces, uint32_t n,
+                                std::vector<uint32_t>* words);
+    int square_namespace_plan(ResidentSquare* sq, const uint8_t* namespaces, uint32_t n, cda_namespace_plan_t* out);
+    int square_namespace_proofs(ResidentSquare* sq, const uint8_t* namespaces, uint32_t n,
+                                const cda_namespace_proofs_out& out);
     // The verifying side: the batch of share_proofs_verify built from the coordinates.
     int sample_proofs_verify(uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
                              const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,
@@ -322,6 +337,10 @@ class Engine {
     // batch on the host, then four launches on the context's stream and one
     // synchronisation; verdict[p] = 0 valid, 1 row proof, 2 share proof.
     int share_proofs_verify(const cda_share_proof_batch* b, uint8_t* verdict);
+    // nmt Proof.VerifyNamespace of every segment of every query against the DAH's row roots, with the DAH's row
+    // selection (verify.hip): verdict[q] = 0 valid, 1 rows, 2 hash or absence leaf, 3 incomplete.
+    int namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const cda_namespace_proof_batch* b,
+                                uint8_t* verdict);
 
     // Stage timing with HIP events on the launch stream (bench / profiling).
     enum Stage { kStageRsQ0 = 0, kStageRsQ3, kStageOrder, kStageLeaves, kStageLevels, kStageDataRoot, kNumStages };

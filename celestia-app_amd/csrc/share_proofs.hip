@@ -30,6 +30,12 @@
 //   the call needs no launch or fill of its own for them.
 // Every index the kernel uses was validated on the host
 // (share_proofs_plan.h).
+//
+// The kernel is driven by a segment table (segment_table.h), and the half that
+// uploads a table, launches and copies back is Engine::emit_segments, which the
+// namespace proofs end in too (namespace_proofs.hip).  Their absence segments
+// (kSegAbsence) have no share units, and their leaf is one more staged slot
+// behind the row root, written packed to absence_leaf.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -38,6 +44,7 @@
 #include "engine.h"
 #include "out_regions.h"
 #include "resident_proof_dev.h"
+#include "segment_table.h"
 #include "sha256_dev.h"
 #include "share_proofs_plan.h"
 #include "tree_index.h"
@@ -47,23 +54,10 @@ namespace cda {
 namespace {
 
 constexpr uint32_t kProofWaves = 4;        // segments, or share units, per workgroup
-constexpr uint32_t kProofSlots = 2 * kProofMaxD + 2;   // proof nodes, the row root, the namespace
-constexpr uint32_t kUnitShares = 16;       // shares one wave copies
+constexpr uint32_t kProofSlots = 2 * kProofMaxD + 2;   // proof nodes, the row root, the namespace or absence leaf
 // The single-range call returns outputs of up to this many bytes in one copy (regions_out): measured against one
 // copy per output, it is faster up to 1 MiB of shares and slower from 2 MiB (profiles/resident_proof_refactor.txt).
 constexpr size_t kOneCopyBytes = 3 << 19;
-
-// One segment, as uploaded: 32 bytes.
-struct SegEntry {
-    uint32_t row;
-    uint32_t range;        // s0 | e0 << 16: the leaf range in the row tree
-    uint32_t node_off;     // first node of the segment in `nodes`
-    uint32_t unit_off;     // first share unit of the segment
-    uint64_t share_off;    // first share of the segment in `shares`
-    uint32_t proof;
-    uint32_t first_cell;   // EDS cell (row * W + col) of the proof's first share
-};
-static_assert(sizeof(SegEntry) == 32);
 
 struct ShareProofsArgs {
     ResidentView sq;
@@ -76,6 +70,7 @@ struct ShareProofsArgs {
     uint8_t* shares;
     uint8_t* namespaces;
     uint32_t* flags;            // one_namespace bytes, preset to 1
+    uint8_t* absence_leaf;      // the namespace proofs' output (namespaces and flags are then NULL)
 };
 
 __device__ __forceinline__ SegEntry load_seg(const SegEntry* p) {
@@ -92,14 +87,16 @@ __device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*sta
     const uint32_t W = 2 * v.k, D = v.log_w, A = D + 1;
     SegEntry e{};
     if (live) e = load_seg(a.segs + g);
-    const uint32_t row = e.row, s0 = e.range & 0xFFFFu, e0 = live ? e.range >> 16 : 1u;
+    const uint32_t row = e.row, s0 = e.range & 0xFFFFu, e0 = live ? (e.range >> 16) & kSegEndMask : 1u;
     const uint32_t cnt = live ? range_proof_count(D, s0, e0) : 0u;
     const bool first = live && e.first_cell == row * W + s0;   // the proof's first segment
+    const bool absent = (e.range & kSegAbsence) != 0;          // an absence segment: its leaf follows the row root
     uint4* st = stage[wave];
     if (live) {
-        // the nodes in proof order, then the row root
-        stage_slots(st, cnt + 1, lane, [&](uint32_t j) {
+        // the nodes in proof order, then the row root, then the leaf of an absence segment
+        stage_slots(st, cnt + 1 + (absent ? 1u : 0u), lane, [&](uint32_t j) {
             if (j == cnt) return StagedSlot{v.root_slots + (uint64_t)row * kSlot, j};
+            if (j == cnt + 1) return StagedSlot{v.levels + ((uint64_t)row * W + s0) * kSlot, j};
             const TreeNode nd = range_proof_node(D, s0, e0, j);
             return StagedSlot{v.levels + level_offset(W, nd.level, 0, kSlot) +
                                   ((uint64_t)row * (W >> nd.level) + nd.index) * kSlot, j};
@@ -107,6 +104,8 @@ __device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*sta
         // the namespace of the proof's first share
         if (first && lane < 2)
             st[stage_row(cnt + 1) + lane] = reinterpret_cast<const uint4*>(v.eds + (uint64_t)e.first_cell * kShare)[lane];
+        // absence_leaf of any other segment is zero
+        if (a.absence_leaf && !absent && lane < kSlotPieces) st[stage_row(cnt + 1) + lane] = make_uint4(0, 0, 0, 0);
         store_root_proof(v.rfc, W, A, row, g, a.leaf_hash, a.aunts, lane);   // Index = row among the 4k roots
     }
     __syncthreads();
@@ -115,6 +114,7 @@ __device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*sta
     if (a.nodes) store_packed<kNode>(sb, cnt, a.nodes + (uint64_t)e.node_off * kNode, lane);
     if (a.row_roots) store_packed<kNode>(sb + cnt * kSlot, 1, a.row_roots + (uint64_t)g * kNode, lane);
     if (a.namespaces && first) store_packed<kNs>(sb + (cnt + 1) * kSlot, 1, a.namespaces + (uint64_t)e.proof * kNs, lane);
+    if (a.absence_leaf) store_packed<kNode>(sb + (cnt + 1) * kSlot, 1, a.absence_leaf + (uint64_t)g * kNode, lane);
 }
 
 // One wavefront per unit of at most kUnitShares shares of one segment.
@@ -130,7 +130,7 @@ __device__ __forceinline__ void share_part(const ShareProofsArgs& a) {
         else hi = mid - 1;
     }
     const SegEntry e = load_seg(a.segs + lo);
-    const uint32_t W = 2 * a.sq.k, s0 = e.range & 0xFFFFu, e0 = e.range >> 16;
+    const uint32_t W = 2 * a.sq.k, s0 = e.range & 0xFFFFu, e0 = (e.range >> 16) & kSegEndMask;
     const uint32_t at = (u - e.unit_off) * kUnitShares;   // first share of the unit within the segment
     const uint32_t cnt = min(kUnitShares, e0 - s0 - at);
     const uint4* src = reinterpret_cast<const uint4*>(a.sq.eds + ((uint64_t)e.row * W + s0 + at) * kShare);
@@ -201,9 +201,10 @@ int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, cons
         return fail(CDA_ERR_INVALID, "the batch has too many shares for one launch");
     // the table, then the one_namespace bytes (1 until a unit finds another namespace), in one upload
     const size_t flag_words = ((size_t)n + 3) / 4;
-    std::vector<uint32_t> up((size_t)S * (sizeof(SegEntry) / 4) + flag_words);
-    SegEntry* segs = reinterpret_cast<SegEntry*>(up.data());
-    std::memset(up.data() + (size_t)S * (sizeof(SegEntry) / 4), 1, flag_words * 4);
+    SegmentEmit em;
+    em.up.resize((size_t)S * kSegWords + flag_words);
+    SegEntry* segs = em.segs();
+    std::memset(em.up.data() + (size_t)S * kSegWords, 1, flag_words * 4);
     uint32_t g = 0, node_at = 0, unit_at = 0;
     uint64_t share_at = 0;
     for (uint32_t i = 0; i < n; i++) {
@@ -218,7 +219,7 @@ int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, cons
             if (o.rfc_total) o.rfc_total[g] = 2ll * W;
             if (o.rfc_index) o.rfc_index[g] = sg.row;
             node_at += count;
-            unit_at += (sg.e0 - sg.s0 + kUnitShares - 1) / kUnitShares;
+            unit_at += seg_units(sg.e0 - sg.s0);
             share_at += sg.e0 - sg.s0;
             g++;
             if (o.node_off) o.node_off[g] = node_at;
@@ -228,30 +229,52 @@ int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, cons
         if (o.start_row) o.start_row[i] = starts[i] / k;
         if (o.end_row) o.end_row[i] = (ends[i] - 1) / k;
     }
+    em.n_segs = S;
+    em.n_units = unit_at;
+    em.n_flags = n;
+    em.node_slots = nmt_count ? (size_t)S * M : plan.n_nodes;
+    em.n_aunts = plan.n_aunts;
+    em.n_shares = plan.n_shares;
+    em.nodes = o.nodes;
+    em.row_roots = o.row_roots;
+    em.leaf_hash = o.rfc_leaf_hash;
+    em.aunts = o.aunts;
+    em.shares = o.shares;
+    em.namespaces = o.namespaces;
+    em.one_namespace = o.one_namespace;
+    em.one_copy_max = one_copy_max;
+    return emit_segments(sq, em);
+}
+
+// The table-to-launch half of both producers (share ranges above, namespaces in namespace_proofs.hip): one
+// upload, one launch whatever the table holds, the requested outputs back.
+int Engine::emit_segments(ResidentSquare* sq, const SegmentEmit& em) {
+    const uint32_t S = em.n_segs;
     // scratch: the upload, then one region per requested output; the flags lie inside the upload
-    OutRegions out(up.size() * 4);
-    const size_t node_slots = nmt_count ? (size_t)S * M : plan.n_nodes;
-    const auto r_nd = out.add(o.nodes, node_slots * kNode), r_rt = out.add(o.row_roots, (size_t)S * kNode),
-               r_lh = out.add(o.rfc_leaf_hash, (size_t)S * 32), r_au = out.add(o.aunts, (size_t)plan.n_aunts * 32),
-               r_sh = out.add(o.shares, (size_t)plan.n_shares * kShare), r_ns = out.add(o.namespaces, (size_t)n * kNs),
-               r_fl = out.add_at(o.one_namespace, (size_t)S * sizeof(SegEntry), n);
+    OutRegions out(em.up.size() * 4);
+    const auto r_nd = out.add(em.nodes, em.node_slots * kNode), r_rt = out.add(em.row_roots, (size_t)S * kNode),
+               r_lh = out.add(em.leaf_hash, (size_t)S * 32), r_au = out.add(em.aunts, em.n_aunts * 32),
+               r_sh = out.add(em.shares, (size_t)em.n_shares * kShare),
+               r_ns = out.add(em.namespaces, (size_t)em.n_flags * kNs),
+               r_al = out.add(em.absence_leaf, (size_t)S * kNode),
+               r_fl = out.add_at(em.one_namespace, (size_t)S * sizeof(SegEntry), em.n_flags);
     hipStream_t s = stream_;
     CDA_TRY(ensure(sq->scratch, out.total(), "hipMalloc"));
     uint8_t* scr = sq->scratch.as<uint8_t>();
-    CDA_TRY(h2d(scr, up.data(), up.size() * 4, s, "H2D share proofs"));
+    CDA_TRY(h2d(scr, em.up.data(), em.up.size() * 4, s, "H2D share proofs"));
     ShareProofsArgs a{sq->view(), reinterpret_cast<const SegEntry*>(scr), S, 0, 0, r_nd.dev(scr), r_rt.dev(scr),
                       r_lh.dev(scr), r_au.dev(scr), r_sh.dev(scr), r_ns.dev(scr),
-                      reinterpret_cast<uint32_t*>(r_fl.dev(scr))};
-    const bool proof_half = a.nodes || a.row_roots || a.leaf_hash || a.aunts || a.namespaces;
+                      reinterpret_cast<uint32_t*>(r_fl.dev(scr)), r_al.dev(scr)};
+    const bool proof_half = a.nodes || a.row_roots || a.leaf_hash || a.aunts || a.namespaces || a.absence_leaf;
     a.proof_blocks = proof_half ? (S + kProofWaves - 1) / kProofWaves : 0;
-    a.n_units = a.shares || a.flags ? unit_at : 0;
+    a.n_units = a.shares || a.flags ? em.n_units : 0;
     const uint32_t blocks = a.proof_blocks + (a.n_units + kProofWaves - 1) / kProofWaves;
     if (blocks) {
         hipLaunchKernelGGL(share_proofs_kernel, dim3(blocks), dim3(64 * kProofWaves), 0, s, a);
         CDA_TRY(launched("share proofs"));
     }
-    // `up` is pageable and the outputs are the caller's: complete before returning
-    return regions_out(out, scr, out.span().bytes <= one_copy_max, s, "D2H share proofs");
+    // the table is pageable and the outputs are the caller's: complete before returning
+    return regions_out(out, scr, out.span().bytes <= em.one_copy_max, s, "D2H share proofs");
 }
 
 }  // namespace cda

@@ -30,8 +30,13 @@
 //                       derived top-down from (index, total).
 //   4. vp_verdict_kernel one lane per proof: 1 if any row proof failed, else 2
 //                       if any NMT proof failed, else 0.
+// Namespace proofs (Engine::namespace_proofs_verify: nmt Proof.VerifyNamespace
+// per row, GetSharesByNamespace's row selection per query) run 1 and 2 on the
+// same batch struct -- an absence segment's one leaf comes from the prover's
+// absence_leaf instead of a hashed share -- then vn_complete_kernel (one lane
+// per proof node: the completeness comparison) and vn_verdict_kernel.
 // Every index a kernel uses was validated on the host (Engine::
-// share_proofs_verify); the counts that are verdicts (aunts, nodes) are
+// share_proofs_verify, namespace_proofs_verify); the counts that are verdicts (aunts, nodes) are
 // compared before anything is read through them.
 #include <cstring>
 #include <string>
@@ -71,6 +76,15 @@ struct VerifyBatch {
     uint8_t* nmt_ok;             // per segment
     uint8_t* row_ok;
     uint8_t* verdict;            // per proof
+    // A namespace batch (namespace_proofs_verify) only; seg_kind == NULL otherwise.  n_shares and leaf_off then
+    // count leaf slots: an inclusion segment's shares, one for an absence segment.
+    const uint8_t* seg_kind;     // per segment: CDA_NAMESPACE_INCLUSION / _ABSENCE
+    const uint64_t* share_off;   // first share of every segment in `shares`
+    const uint8_t* absence_leaf; // per segment, node_len bytes: the leaf an absence segment folds
+    const uint32_t* seg_row;     // per segment: its row in the DAH
+    const uint8_t* dah_roots;    // n_rows row roots of the DAH
+    uint32_t n_rows, n_nodes;
+    uint8_t* comp_ok;            // per segment, preset to 1: no proof node contradicts completeness
 };
 
 // Leaf nodes of every share of the batch.  FAST: ns_len 29, share_len 512,
@@ -87,8 +101,17 @@ __global__ __launch_bounds__(256) void vp_leaf_kernel(const VerifyBatch b) {
         else hi = mid;
     }
     const uint8_t* nid = b.namespaces + (size_t)b.seg_proof[lo] * b.ns_len;
-    const uint8_t* share = b.shares + i * b.share_len;
     uint8_t* out = b.buf_a + i * b.stride;
+    uint64_t at = i;   // the share of leaf slot i
+    if (b.seg_kind) {
+        if (b.seg_kind[lo] == CDA_NAMESPACE_ABSENCE) {   // the prover's leaf node enters the fold as it is
+            const uint8_t* leaf = b.absence_leaf + (size_t)lo * b.node_len;
+            for (uint32_t j = 0; j < b.stride; j++) out[j] = j < b.node_len ? leaf[j] : (uint8_t)0;
+            return;
+        }
+        at = b.share_off[lo] + (i - b.leaf_off[lo]);
+    }
+    const uint8_t* share = b.shares + at * b.share_len;
     uint32_t d[8];
     if constexpr (FAST) {
         uint32_t nsw[8];
@@ -285,6 +308,58 @@ __global__ __launch_bounds__(256) void vp_verdict_kernel(const VerifyBatch b) {
     b.verdict[p] = (uint8_t)v;
 }
 
+// bytes.Compare of two namespaces of n bytes: -1, 0, 1.
+__device__ __forceinline__ int vn_cmp(const uint8_t* a, const uint8_t* b, uint32_t n) {
+    for (uint32_t j = 0; j < n; j++)
+        if (a[j] != b[j]) return a[j] < b[j] ? -1 : 1;
+    return 0;
+}
+
+// nmt VerifyLeafHashes' completeness check, one lane per proof node: a node left of the range (the first
+// popcount(start) of its segment) must have a max namespace below ns, a later one a min namespace above it.
+__global__ __launch_bounds__(256) void vn_complete_kernel(const VerifyBatch b) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= b.n_nodes) return;
+    // the segment that owns node i: node_off[s] <= i < node_off[s + 1]
+    uint32_t lo = 0, hi = b.n_segs;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (b.node_off[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    const uint8_t* ns = b.namespaces + (size_t)b.seg_proof[lo] * b.ns_len;
+    const uint8_t* node = b.nodes + (size_t)i * b.node_len;
+    const bool left = i - b.node_off[lo] < (uint32_t)__popc((uint32_t)b.nmt_start[lo]);
+    const bool bad = left ? vn_cmp(node + b.ns_len, ns, b.ns_len) >= 0 : vn_cmp(node, ns, b.ns_len) <= 0;
+    if (bad) b.comp_ok[lo] = 0;
+}
+
+// One lane per query: the rows the DAH selects against the answer's rows (1), then the segments' folds and
+// absence leaves (2), then completeness (3).
+__global__ __launch_bounds__(256) void vn_verdict_kernel(const VerifyBatch b) {
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= b.n_proofs) return;
+    const uint8_t* ns = b.namespaces + (size_t)p * b.ns_len;
+    const uint32_t s0 = b.seg_off[p], s1 = b.seg_off[p + 1];
+    uint32_t s = s0;
+    bool rows_ok = true;
+    for (uint32_t r = 0; r < b.n_rows; r++) {
+        const uint8_t* root = b.dah_roots + (size_t)r * b.node_len;
+        if (vn_cmp(root, ns, b.ns_len) > 0 || vn_cmp(ns, root + b.ns_len, b.ns_len) > 0) continue;
+        if (s < s1 && b.seg_row[s] == r) s++;
+        else rows_ok = false;
+    }
+    uint32_t v = rows_ok && s == s1 ? 0 : 1;
+    if (v == 0) {
+        for (s = s0; s < s1; s++) {
+            const bool absence = b.seg_kind[s] == CDA_NAMESPACE_ABSENCE;
+            if (!b.nmt_ok[s] || (absence && vn_cmp(b.absence_leaf + (size_t)s * b.node_len, ns, b.ns_len) <= 0)) v = 2;
+            else if (!b.comp_ok[s] && v == 0) v = 3;
+        }
+    }
+    b.verdict[p] = (uint8_t)v;
+}
+
 std::string at(uint32_t proof, const char* what) { return "proof " + std::to_string(proof) + ": " + what; }
 
 }  // namespace
@@ -432,6 +507,161 @@ int Engine::share_proofs_verify(const cda_share_proof_batch* b, uint8_t* verdict
     }
     hipLaunchKernelGGL(vp_verdict_kernel, dim3((P + 255) / 256), dim3(256), 0, s, v);
     CDA_TRY(launched("proof verdicts"));
+    std::vector<uint8_t> out(P);
+    CDA_TRY(d2h(out.data(), v.verdict, P, s, "D2H verdicts"));
+    CDA_TRY(sync(s));
+    memcpy(verdict, out.data(), P);
+    return CDA_OK;
+}
+
+// nmt Proof.VerifyNamespace per segment and GetSharesByNamespace's row selection per query.  The leaf and fold
+// kernels are the share proofs': a segment's row root is the DAH's (gathered here by the segment's row), an
+// absence segment folds the one leaf it brings.  Five launches and one fill per batch.
+int Engine::namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const cda_namespace_proof_batch* b,
+                                    uint8_t* verdict) {
+    if (!b) return fail(CDA_ERR_INVALID, "null batch");
+    CDA_TRY(check_width(k));
+    const uint32_t P = b->n_queries, W = 2 * k;
+    if (P == 0) return CDA_OK;
+    if (!verdict) return fail(CDA_ERR_INVALID, "null verdict buffer");
+    if (!row_roots || !b->namespaces || !b->seg_off) return fail(CDA_ERR_INVALID, "null row_roots / namespaces / seg_off");
+    auto query = [](uint32_t q, const std::string& what) { return "query " + std::to_string(q) + ": " + what; };
+    for (uint32_t q = 0; q < P; q++) {
+        bool parity = true;
+        for (int j = 0; j < kNs; j++) parity = parity && b->namespaces[(size_t)q * kNs + j] == 0xFFu;
+        if (parity) return fail(CDA_ERR_INVALID, query(q, "namespace is the parity shares namespace"));
+    }
+    if (b->seg_off[0] != 0) return fail(CDA_ERR_INVALID, query(0, "seg_off must start at 0"));
+    for (uint32_t q = 0; q < P; q++)
+        if (b->seg_off[q + 1] < b->seg_off[q]) return fail(CDA_ERR_INVALID, query(q, "seg_off decreases"));
+    const uint32_t S = b->seg_off[P];
+    if (S && (!b->row || !b->kind || !b->nmt_start || !b->nmt_end || !b->node_off || !b->share_off))
+        return fail(CDA_ERR_INVALID, "null segment field (row / kind / nmt_start / nmt_end / node_off / share_off)");
+    if (S && ((b->n_nodes && !b->nodes) || (b->n_shares && !b->shares)))
+        return fail(CDA_ERR_INVALID, "null nodes / shares");
+    std::vector<uint32_t> seg_query(S);
+    for (uint32_t q = 0; q < P; q++)
+        for (uint32_t s = b->seg_off[q]; s < b->seg_off[q + 1]; s++) seg_query[s] = q;
+    std::vector<uint64_t> leaf_off(S + 1, 0);
+    std::vector<uint8_t> seg_roots((size_t)S * kNode);
+    if (S) {
+        if (b->node_off[0] != 0) return fail(CDA_ERR_INVALID, query(0, "node_off must start at 0"));
+        if (b->share_off[0] != 0) return fail(CDA_ERR_INVALID, query(0, "share_off must start at 0"));
+    }
+    uint64_t share_at = 0;
+    for (uint32_t s = 0; s < S; s++) {
+        const int32_t st = b->nmt_start[s], en = b->nmt_end[s];
+        auto seg = [&](const std::string& what) {
+            return fail(CDA_ERR_INVALID, query(seg_query[s], "segment " + std::to_string(s) + ": " + what));
+        };
+        const uint8_t kind = b->kind[s];
+        if (kind != CDA_NAMESPACE_INCLUSION && kind != CDA_NAMESPACE_ABSENCE)
+            return seg("kind " + std::to_string(kind) + " is neither 1 (inclusion) nor 2 (absence)");
+        if (b->row[s] >= W) return seg("row " + std::to_string(b->row[s]) + " is not below " + std::to_string(W));
+        if (st < 0) return seg("nmt_start " + std::to_string(st) + " is negative");
+        if (en <= st) return seg("nmt_end " + std::to_string(en) + " is not above nmt_start " + std::to_string(st));
+        if ((uint32_t)en > W) return seg("nmt_end " + std::to_string(en) + " exceeds " + std::to_string(W));
+        if (kind == CDA_NAMESPACE_ABSENCE && en != st + 1)
+            return seg("an absence segment's nmt_end " + std::to_string(en) + " is not nmt_start + 1");
+        if (kind == CDA_NAMESPACE_ABSENCE && !b->absence_leaf) return seg("null absence_leaf");
+        if (b->node_off[s + 1] < b->node_off[s]) return seg("node_off decreases");
+        if (b->share_off[s + 1] < b->share_off[s]) return seg("share_off decreases");
+        if (b->share_off[s] != share_at)
+            return seg("share_off " + std::to_string(b->share_off[s]) + " is not the " + std::to_string(share_at) +
+                       " shares of the inclusion segments before it");
+        share_at += kind == CDA_NAMESPACE_INCLUSION ? (uint64_t)(en - st) : 0;
+        leaf_off[s + 1] = leaf_off[s] + (uint64_t)(en - st);
+        memcpy(seg_roots.data() + (size_t)s * kNode, row_roots + (size_t)b->row[s] * kNode, kNode);
+    }
+    if (S && b->node_off[S] != b->n_nodes)
+        return fail(CDA_ERR_INVALID, "node_off ends at " + std::to_string(b->node_off[S]) + ", n_nodes is " +
+                                         std::to_string(b->n_nodes));
+    if (S && b->share_off[S] != share_at)
+        return fail(CDA_ERR_INVALID, "share_off ends at " + std::to_string(b->share_off[S]) +
+                                         ", the inclusion segments' nmt_end - nmt_start sum to " +
+                                         std::to_string(share_at));
+    if (share_at != b->n_shares)
+        return fail(CDA_ERR_INVALID, "n_shares is " + std::to_string(b->n_shares) +
+                                         ", the inclusion segments' nmt_end - nmt_start sum to " +
+                                         std::to_string(share_at));
+
+    hipStream_t s = stream_;
+    const uint64_t n_leaves = leaf_off[S];
+    const uint32_t n_nodes = S ? b->n_nodes : 0;
+    // one input buffer, every array at a 16-byte boundary
+    struct Piece {
+        const void* host;
+        size_t bytes, off;
+    };
+    size_t total = 0;
+    auto piece = [&](const void* host, size_t bytes) {
+        Piece pc{host, host ? bytes : 0, total};
+        total += (pc.bytes + 15) & ~(size_t)15;
+        return pc;
+    };
+    const Piece p_ns = piece(b->namespaces, (size_t)P * kNs), p_seg = piece(b->seg_off, (size_t)(P + 1) * 4),
+                p_sq = piece(seg_query.data(), (size_t)S * 4), p_row = piece(b->row, (size_t)S * 4),
+                p_kind = piece(b->kind, S), p_st = piece(b->nmt_start, (size_t)S * 4),
+                p_en = piece(b->nmt_end, (size_t)S * 4), p_no = piece(b->node_off, S ? (size_t)(S + 1) * 4 : 0),
+                p_nodes = piece(b->nodes, (size_t)n_nodes * kNode), p_rr = piece(seg_roots.data(), (size_t)S * kNode),
+                p_dah = piece(row_roots, (size_t)W * kNode), p_lo = piece(leaf_off.data(), (size_t)(S + 1) * 8),
+                p_so = piece(b->share_off, S ? (size_t)(S + 1) * 8 : 0),
+                p_sh = piece(b->shares, (size_t)share_at * kShare),
+                p_al = piece(b->absence_leaf, (size_t)S * kNode);
+    CDA_TRY(ensure(vp_in_, total + 16, "hipMalloc proof batch"));
+    const size_t scr_nodes = ((size_t)n_leaves * kSlot + 15) & ~(size_t)15;
+    const size_t flags = ((size_t)S + 15) & ~(size_t)15;
+    const size_t node_slots = (size_t)n_nodes * kSlot;
+    CDA_TRY(ensure(vp_scratch_, 2 * scr_nodes + node_slots + 2 * flags + P + 16, "hipMalloc proof scratch"));
+    uint8_t* in = vp_in_.as<uint8_t>();
+    for (const Piece* pc : {&p_ns, &p_seg, &p_sq, &p_row, &p_kind, &p_st, &p_en, &p_no, &p_nodes, &p_rr, &p_dah, &p_lo,
+                            &p_so, &p_sh, &p_al})
+        if (pc->bytes) CDA_TRY(h2d(in + pc->off, pc->host, pc->bytes, s, "H2D namespace proof batch"));
+    uint8_t* scr = vp_scratch_.as<uint8_t>();
+    VerifyBatch v{};
+    v.n_proofs = P;
+    v.n_segs = S;
+    v.ns_len = kNs;
+    v.share_len = kShare;
+    v.node_len = kNode;
+    v.stride = kSlot;
+    v.namespaces = in + p_ns.off;
+    v.seg_off = reinterpret_cast<const uint32_t*>(in + p_seg.off);
+    v.seg_proof = reinterpret_cast<const uint32_t*>(in + p_sq.off);
+    v.nmt_start = reinterpret_cast<const int32_t*>(in + p_st.off);
+    v.nmt_end = reinterpret_cast<const int32_t*>(in + p_en.off);
+    v.node_off = reinterpret_cast<const uint32_t*>(in + p_no.off);
+    v.nodes = in + p_nodes.off;
+    v.row_roots = in + p_rr.off;
+    v.shares = in + p_sh.off;
+    v.leaf_off = reinterpret_cast<const uint64_t*>(in + p_lo.off);
+    v.n_shares = n_leaves;
+    v.buf_a = scr;
+    v.buf_b = scr + scr_nodes;
+    v.node_slots = scr + 2 * scr_nodes;
+    v.nmt_ok = v.node_slots + node_slots;
+    v.comp_ok = v.nmt_ok + flags;
+    v.verdict = v.comp_ok + flags;
+    v.seg_kind = in + p_kind.off;
+    v.share_off = reinterpret_cast<const uint64_t*>(in + p_so.off);
+    v.absence_leaf = in + p_al.off;
+    v.seg_row = reinterpret_cast<const uint32_t*>(in + p_row.off);
+    v.dah_roots = in + p_dah.off;
+    v.n_rows = W;
+    v.n_nodes = n_nodes;
+    if (S) {
+        hipLaunchKernelGGL(vp_leaf_kernel<true>, dim3((uint32_t)((n_leaves + 255) / 256)), dim3(256), 0, s, v);
+        CDA_TRY(launched("namespace proof leaves"));
+        hipLaunchKernelGGL(vp_fold_kernel<true>, dim3(S), dim3(64), 0, s, v);
+        CDA_TRY(launched("namespace proof range fold"));
+        CDA_TRY(fill(v.comp_ok, 1, S, s, "namespace proof completeness flags"));
+        if (n_nodes) {
+            hipLaunchKernelGGL(vn_complete_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, s, v);
+            CDA_TRY(launched("namespace proof completeness"));
+        }
+    }
+    hipLaunchKernelGGL(vn_verdict_kernel, dim3((P + 255) / 256), dim3(256), 0, s, v);
+    CDA_TRY(launched("namespace proof verdicts"));
     std::vector<uint8_t> out(P);
     CDA_TRY(d2h(out.data(), v.verdict, P, s, "D2H verdicts"));
     CDA_TRY(sync(s));

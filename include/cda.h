@@ -45,6 +45,11 @@
  *   cda_square_share_proofs / cda_square_share_proofs_plan
  *                          NewShareInclusionProofFromEDS for many ranges of one
  *                          square in one launch, as a cda_share_proof_batch
+ *   cda_square_namespace_plan / cda_square_namespace_proofs / cda_namespace_proofs_verify
+ *                          all shares of many namespaces of one square with nmt
+ *                          ProveNamespace's proofs (EXT nmt v0.22.0; absence proofs
+ *                          included), the rows chosen as GetSharesByNamespace chooses
+ *                          them from the DAH, and Proof.VerifyNamespace of the answers
  *   cda_nmt_axis_root(s) / cda_nmt_prove_range
  *                          wrapper.NewErasuredNamespacedMerkleTree + Push +
  *                          Root / ProveRange (pkg/wrapper/nmt_wrapper.go:55-129)
@@ -433,7 +438,8 @@ int cda_square_dah(cda_square *sq, uint32_t *k, uint8_t *row_roots, uint8_t *col
  *   nmt_start/end R entries: NMTProof.Start / End (leaf range in the row)
  *   nmt_count     R entries; nmt_nodes R*M*90 B: NMTProof.Nodes of row i at
  *                 [i*M*90, ...) (nmt ProveRange order: maximal subtrees outside
- *                 the range, left to right); NMTProof.LeafHash is empty
+ *                 the range, left to right); NMTProof.LeafHash is empty (only
+ *                 cda_square_namespace_proofs' absence segments carry one)
  *   row_roots     R*90: RowProof.RowRoots
  *   row_leaf_hash R*32, row_aunts R*A*32: RowProof.Proofs (merkle proofs of
  *                 the rows among rowRoots || colRoots: Total 4k, Index = row,
@@ -542,6 +548,84 @@ typedef struct cda_share_proofs_out {
  * cda_square_share_proof returns the same bytes for one range per call. */
 int cda_square_share_proofs(cda_square *sq, const uint32_t *starts, const uint32_t *ends, uint32_t n,
                             const cda_share_proofs_out *out);
+
+/* ---- All shares of a namespace, with completeness proofs -----------------------
+ * nmt v0.22.0 ProveNamespace and Proof.VerifyNamespace (VerifyLeafHashes with verifyCompleteness = true)
+ * over the row trees of a resident square, and the row selection GetSharesByNamespace does on the DAH, for
+ * n namespaces (29 bytes each) in one call.  Per query ns and row r:
+ *   - r is selected iff min(rowRoot_r) <= ns <= max(rowRoot_r) (the square's own roots, IgnoreMaxNamespace);
+ *     only rows < k can be, and rows that are not selected do not appear;
+ *   - start = the leaves of the row with namespace < ns, end = start + those with namespace == ns;
+ *   - kind 1 (inclusion, end > start): leaf range [start, end), the shares row[start:end] and the nodes of
+ *     ProveRange(start, end) in cda_square_share_proofs' order;
+ *   - kind 2 (absence, end == start, and then start < k): leaf range [start, start + 1), the nodes of
+ *     ProveRange(start, start + 1), the 90-byte leaf node of leaf `start` (NMTProof.LeafHash), no shares.
+ * A query's segments are in ascending row order; it may have none (ns below, above or between the rows).
+ * The arrays carry cda_share_proofs_out's names and layouts where the meaning is the same (S segments in all):
+ *   seg_off n+1; row S; kind S bytes; nmt_start / nmt_end S; node_off S+1; nodes n_nodes*90;
+ *   share_off S+1 (in shares); shares n_shares*512; absence_leaf S*90 (zero for inclusion segments).
+ *
+ * cda_square_namespace_plan: the sizes to allocate.  It runs the search on the GPU: one launch, and one
+ * word per (query, row < k) copied back (n*k*4 bytes).  n == 0: CDA_OK, all sizes zero.
+ * cda_square_namespace_proofs: caller-allocated host buffers, any of them NULL; complete on return.  It
+ * runs the search again (it keeps no state and trusts no table of the caller's): one search launch, one
+ * host pass over the words, one launch of cda_square_share_proofs' kernel, whatever n and the run lengths.
+ * Both: CDA_ERR_INVALID, outputs untouched, with a message naming the query for a query equal to
+ * ParitySharesNamespace (29 x 0xFF) and for null arrays; a square created with CDA_ERR_PUSH_ORDER answers
+ * CDA_ERR_PUSH_ORDER (nmt could not have built its trees), outputs untouched. */
+typedef struct cda_namespace_plan_t {
+    uint64_t n_segments, n_nodes, n_shares;
+} cda_namespace_plan_t;
+int cda_square_namespace_plan(cda_square *sq, const uint8_t *namespaces, uint32_t n, cda_namespace_plan_t *out);
+typedef struct cda_namespace_proofs_out {
+    uint32_t *seg_off;
+    uint32_t *row;
+    uint8_t *kind;
+    int32_t *nmt_start;
+    int32_t *nmt_end;
+    uint32_t *node_off;
+    uint8_t *nodes;
+    uint64_t *share_off;
+    uint8_t *shares;
+    uint8_t *absence_leaf;
+} cda_namespace_proofs_out;
+int cda_square_namespace_proofs(cda_square *sq, const uint8_t *namespaces, uint32_t n,
+                                const cda_namespace_proofs_out *out);
+/* The verifying side, for a square of ODS width k whose DAH the caller trusts (row_roots: 2k*90).  The
+ * arrays are the prover's, by pointer assignment; the row root of every segment is row_roots[row], never
+ * the prover's.  verdict[q] (n_queries bytes), the lower number wins:
+ *   0 valid;
+ *   1 the answer's rows are not exactly the rows the DAH selects for the namespace, in ascending order;
+ *   2 a segment does not hash to its row root (VerifyLeafHashes' root comparison; too few or too many
+ *     nodes for the range too), or an absence segment's leaf does not have a min namespace > ns;
+ *   3 the proof is incomplete: one of the first popcount(nmt_start) nodes (left of the range) has a max
+ *     namespace >= ns, or a later node has a min namespace <= ns.
+ * Checked on the host before anything is enqueued, CDA_ERR_INVALID with a message naming the query or the
+ * segment and the field, verdict untouched: null arrays; a query equal to ParitySharesNamespace; offsets
+ * that do not start at 0, decrease or do not end at the counts; kind not 1 or 2; not 0 <= nmt_start <
+ * nmt_end <= 2k; an absence segment with nmt_end != nmt_start + 1; row >= 2k; share_off not the running
+ * sum of the inclusion segments' lengths, or that sum not n_shares; k not a power of two <= 1024.
+ * n_queries == 0 returns CDA_OK. */
+#define CDA_NAMESPACE_INCLUSION 1
+#define CDA_NAMESPACE_ABSENCE 2
+typedef struct cda_namespace_proof_batch {
+    uint32_t n_queries;
+    const uint8_t *namespaces;     /* n_queries*29 */
+    const uint32_t *seg_off;       /* n_queries+1; S = last */
+    const uint32_t *row;           /* S */
+    const uint8_t *kind;           /* S: CDA_NAMESPACE_INCLUSION / CDA_NAMESPACE_ABSENCE */
+    const int32_t *nmt_start;      /* S */
+    const int32_t *nmt_end;        /* S */
+    const uint32_t *node_off;      /* S+1 */
+    const uint8_t *nodes;          /* n_nodes*90 */
+    uint32_t n_nodes;
+    const uint64_t *share_off;     /* S+1, in shares */
+    const uint8_t *shares;         /* n_shares*512 */
+    uint64_t n_shares;
+    const uint8_t *absence_leaf;   /* S*90: read for absence segments only */
+} cda_namespace_proof_batch;
+int cda_namespace_proofs_verify(cda_ctx *ctx, uint32_t k, const uint8_t *row_roots,
+                                const cda_namespace_proof_batch *b, uint8_t *verdict);
 
 /* ---- Repair ------------------------------------------
  * rsmt2d ExtendedDataSquare.Repair(rowRoots, colRoots) (EXT v0.14.0,
