@@ -191,6 +191,9 @@ struct Forest2 {
 // HashNode of two big-endian child slots -> parent slot (little-endian words,
 // as stored).  Block 0 = 0x01 || L[0:63]: a parity left child makes words
 // 0..13 constant, so those nodes start from the precomputed mid-state (MID).
+// The test covers all 55 bytes of L in those words (is_parity_head): in an
+// ordered tree min = 0xFF*29 alone implies them, in the blind tree of an
+// unordered square (whose roots the library still writes) it does not.
 // The branch is worth it only where a wave's parents are all of one kind
 // (level_kernel orders them so); otherwise both paths run (MID = false).
 template <bool MID = true>
@@ -203,7 +206,7 @@ __device__ __forceinline__ void hash_node(const uint32_t (&L)[kSlotWords], const
     // literals saves ~1.5% of its rotations but duplicates blocks 1-2 per
     // branch: ~8.2k instead of ~5.5k instructions, past the instruction cache
     // a CU pair shares -- not taken.)
-    if (MID && is_parity_min(L)) {
+    if (MID && is_parity_head(L)) {
         w[14] = node_msg(L, R, 14);
         w[15] = node_msg(L, R, 15);
         sha_compress_from<kNodeParityRounds>(st, kNodeParityMid, kNodeParityHead, w);
@@ -231,8 +234,9 @@ __device__ __forceinline__ void level_block(const Forest2& fs, uint32_t n_in, ui
     uint32_t t, p;
     if (F.node_stride == 1) {
         // all trees' left-half parents first, then the right halves: a wave
-        // then never mixes parents with a data and a parity left child (the
-        // mid-state branch below stays uniform); runs of n_out/2 parents of
+        // then never mixes parents with a data and a parity left child (on
+        // an ordered square the mid-state branch below stays uniform; the
+        // blind trees of an unordered one may diverge); runs of n_out/2 parents of
         // one tree remain adjacent, so slot loads stay coalesced
         if (n_out >= 2) {
             const uint32_t hn = n_out / 2, per = F.n_trees * hn;

@@ -26,6 +26,9 @@
  *                                         (every cell hashed once per axis), used
  *                                         only as bench.py's CPU baseline and
  *                                         tested bit-equal to the scalar path.
+ * oracle_blind_dah / oracle_blind_extend_dah run either one with the push-order
+ * check skipped (the reference's BlindTree, test/util/malicious/tree.go): the
+ * roots the library writes beside CDA_ERR_PUSH_ORDER.
  */
 #include <pthread.h>
 #include <stdint.h>
@@ -468,15 +471,18 @@ void oracle_hash_node(const uint8_t l[NODE], const uint8_t r[NODE], uint8_t out[
 
 /* Root of one row (col=0) or column (col=1): W leaves, W a power of two.
  * Returns 0, or -3 on namespace push-order violation (nmt ErrInvalidPushOrder);
- * on error *bad_pos receives the index of the offending push. */
-static int axis_root(const uint8_t *eds, uint32_t k, int col, uint32_t idx, uint8_t out[NODE], uint32_t *bad_pos) {
+ * on error *bad_pos receives the index of the offending push.  blind: the
+ * reference's BlindTree (test/util/malicious/tree.go:18-58, ForceAddLeaf) --
+ * the same leaves and nodes with the push-order check skipped. */
+static int axis_root(const uint8_t *eds, uint32_t k, int col, uint32_t idx, uint8_t out[NODE], uint32_t *bad_pos,
+                     int blind) {
     uint32_t W = 2 * k;
     uint8_t *nodes = malloc((size_t)W * NODE);
     const uint8_t *last = NULL;
     for (uint32_t j = 0; j < W; j++) {
         const uint8_t *cell = col ? CELL(eds, W, j, idx) : CELL(eds, W, idx, j);
         const uint8_t *ns = (j < k && idx < k) ? cell : PARITY_NS;
-        if (last && memcmp(ns, last, NS) < 0) { free(nodes); if (bad_pos) *bad_pos = j; return -3; }
+        if (!blind && last && memcmp(ns, last, NS) < 0) { free(nodes); if (bad_pos) *bad_pos = j; return -3; }
         last = ns;
         oracle_hash_leaf(ns, cell, nodes + (size_t)j * NODE);
     }
@@ -495,7 +501,7 @@ int oracle_roots(const uint8_t *eds, uint32_t k, uint8_t *rows, uint8_t *cols, i
     for (int ax = 0; ax < 2; ax++)
         for (uint32_t i = 0; i < W; i++) {
             uint32_t pos;
-            if (axis_root(eds, k, ax, i, (ax ? cols : rows) + (size_t)i * NODE, &pos)) {
+            if (axis_root(eds, k, ax, i, (ax ? cols : rows) + (size_t)i * NODE, &pos, 0)) {
                 if (err_axis) *err_axis = ax;
                 if (err_idx) *err_idx = i;
                 return -3;
@@ -581,7 +587,7 @@ void oracle_random_square(uint32_t k, uint64_t square_index, uint8_t *ods) {
 /* ------------------------------------------------------------------ */
 typedef struct {
     uint8_t *eds; uint32_t k; int phase; uint32_t next; pthread_mutex_t mu;
-    uint8_t *rows, *cols; int err;
+    uint8_t *rows, *cols; int err; int blind;
 } job;
 
 static void *worker(void *arg) {
@@ -601,7 +607,8 @@ static void *worker(void *arg) {
         } else {                        /* roots: one tree per task, each cell hashed per axis */
             if (t >= 2 * W) break;
             int ax = t & 1; uint32_t i = t >> 1;
-            if (axis_root(j->eds, j->k, ax, i, (ax ? j->cols : j->rows) + (size_t)i * NODE, NULL)) j->err = -3;
+            if (axis_root(j->eds, j->k, ax, i, (ax ? j->cols : j->rows) + (size_t)i * NODE, NULL, j->blind))
+                j->err = -3;
         }
     }
     return NULL;
@@ -625,11 +632,51 @@ int oracle_cpu_baseline(const uint8_t *ods, uint32_t k, uint8_t *eds, uint8_t *r
     if (nthreads < 1) nthreads = 1;
     uint32_t W = 2 * k;
     for (uint32_t r = 0; r < k; r++) memcpy(CELL(eds, W, r, 0), ods + (size_t)r * k * SHARE, (size_t)k * SHARE);
-    job j = {eds, k, 0, 0, PTHREAD_MUTEX_INITIALIZER, rows, cols, 0};
+    job j = {eds, k, 0, 0, PTHREAD_MUTEX_INITIALIZER, rows, cols, 0, 0};
     run_phase(&j, 0, nthreads);
     run_phase(&j, 1, nthreads);
     run_phase(&j, 2, nthreads);
     if (j.err) return j.err;
+    oracle_data_root(rows, cols, W, root);
+    return 0;
+}
+
+/* Row roots, column roots and data root of an EDS over BlindTrees (the
+ * malicious package's NewDataAvailabilityHeader): oracle_roots +
+ * oracle_data_root with the push-order check skipped, so an unordered square
+ * has roots too; on an ordered square they equal the honest ones.
+ * nthreads = 0: the scalar checker path; > 0: the CPU baseline's workers. */
+int oracle_blind_dah(const uint8_t *eds, uint32_t k, uint8_t *rows, uint8_t *cols, uint8_t root[32], int nthreads) {
+    if (k == 0 || (k & (k - 1))) return -1;
+    uint32_t W = 2 * k;
+    if (nthreads <= 0) {
+        for (int ax = 0; ax < 2; ax++)
+            for (uint32_t i = 0; i < W; i++)
+                axis_root(eds, k, ax, i, (ax ? cols : rows) + (size_t)i * NODE, NULL, 1);
+    } else {
+        job j = {(uint8_t *)eds, k, 0, 0, PTHREAD_MUTEX_INITIALIZER, rows, cols, 0, 1};
+        run_phase(&j, 2, nthreads);
+    }
+    oracle_data_root(rows, cols, W, root);
+    return 0;
+}
+
+/* malicious.ExtendShares + the blind header: oracle_extend_dah (nthreads = 0)
+ * / oracle_cpu_baseline (nthreads > 0) with the push-order check skipped. */
+int oracle_blind_extend_dah(const uint8_t *ods, uint32_t k, uint8_t *eds, uint8_t *rows, uint8_t *cols,
+                            uint8_t root[32], int nthreads) {
+    if (nthreads <= 0) {
+        int rc = oracle_extend(ods, k, eds);
+        return rc ? rc : oracle_blind_dah(eds, k, rows, cols, root, 0);
+    }
+    pthread_once(&fields_once, fields_init);
+    if (k == 0 || (k & (k - 1))) return -1;
+    uint32_t W = 2 * k;
+    for (uint32_t r = 0; r < k; r++) memcpy(CELL(eds, W, r, 0), ods + (size_t)r * k * SHARE, (size_t)k * SHARE);
+    job j = {eds, k, 0, 0, PTHREAD_MUTEX_INITIALIZER, rows, cols, 0, 1};
+    run_phase(&j, 0, nthreads);
+    run_phase(&j, 1, nthreads);
+    run_phase(&j, 2, nthreads);
     oracle_data_root(rows, cols, W, root);
     return 0;
 }

@@ -36,6 +36,8 @@ def lib():
         L.oracle_data_root.argtypes = [u8p, u8p, C.c_uint32, u8p]
         L.oracle_extend_dah.argtypes = [u8p, C.c_uint32, u8p, u8p, u8p, u8p]
         L.oracle_cpu_baseline.argtypes = [u8p, C.c_uint32, u8p, u8p, u8p, u8p, C.c_int]
+        L.oracle_blind_dah.argtypes = [u8p, C.c_uint32, u8p, u8p, u8p, C.c_int]
+        L.oracle_blind_extend_dah.argtypes = [u8p, C.c_uint32, u8p, u8p, u8p, u8p, C.c_int]
         L.oracle_random_square.argtypes = [C.c_uint32, C.c_uint64, u8p]
         L.oracle_leopard_encode.argtypes = [u8p, u8p, C.c_uint32, C.c_uint32]
         L.oracle_table.argtypes = [C.c_int, C.c_int]
@@ -125,6 +127,39 @@ def cpu_baseline(ods: np.ndarray, nthreads: int):
     rc = lib().oracle_cpu_baseline(_p(ods), k, _p(eds), _p(rows), _p(cols), _p(root), nthreads)
     if rc:
         raise ValueError(f"oracle_cpu_baseline rc={rc}")
+    return eds, rows, cols, root.tobytes()
+
+
+def blind_dah(eds: np.ndarray, k: int, nthreads: int = 0):
+    """Row roots, column roots and data root of `eds` over BlindTrees (no
+    push-order check; test/util/malicious tree.go / hasher.go): what the
+    library writes beside CDA_ERR_PUSH_ORDER.  Equal to roots() + data_root()
+    on an ordered square."""
+    eds = np.ascontiguousarray(eds, dtype=np.uint8)
+    W = 2 * k
+    assert eds.size == W * W * SHARE
+    rows = np.empty((W, NODE), dtype=np.uint8)
+    cols = np.empty((W, NODE), dtype=np.uint8)
+    root = np.empty(32, dtype=np.uint8)
+    rc = lib().oracle_blind_dah(_p(eds), k, _p(rows), _p(cols), _p(root), nthreads)
+    if rc:
+        raise ValueError(f"oracle_blind_dah rc={rc}")
+    return rows, cols, root.tobytes()
+
+
+def blind_extend_dah(ods: np.ndarray, nthreads: int = 0):
+    """extend_dah (nthreads = 0) / cpu_baseline (nthreads > 0) with the
+    push-order check skipped: (eds, rows, cols, root) of any square."""
+    ods = np.ascontiguousarray(ods, dtype=np.uint8).reshape(-1, SHARE)
+    k = int(round(ods.shape[0] ** 0.5))
+    W = 2 * k
+    eds = np.empty((W * W, SHARE), dtype=np.uint8)
+    rows = np.empty((W, NODE), dtype=np.uint8)
+    cols = np.empty((W, NODE), dtype=np.uint8)
+    root = np.empty(32, dtype=np.uint8)
+    rc = lib().oracle_blind_extend_dah(_p(ods), k, _p(eds), _p(rows), _p(cols), _p(root), nthreads)
+    if rc:
+        raise ValueError(f"oracle_blind_extend_dah rc={rc}")
     return eds, rows, cols, root.tobytes()
 
 

@@ -14,7 +14,8 @@ a plan the default schedule does not.
 GPU part: one in-place device batch per SWEEP row, every square's EDS, packed
 row / column roots and data root bit-exact against the C oracle (k = 128:
 the committed oracle digests of tests/golden/config4_k128*.json), and the
-push-order status and detail of a square with two Q0 namespaces swapped.
+push-order status and detail of a square with two Q0 namespaces swapped, whose
+roots are the blind oracle's up to k = 128.
 
 A changed threshold in hash_plan.h must come with a SWEEP row: the coverage
 test names the (k, n) to add."""
@@ -219,8 +220,9 @@ def _swapped(k):
 def _expected(k, j, bad):
     """Oracle outputs of distinct square j of width k (cached for the k in
     hand): (ods, eds, rows, cols, root, detail); a digest dict instead of the
-    bytes at k = 128; rows = cols = root = None for the swapped square (the
-    oracle refuses its roots; its EDS is checked up to k = 128)."""
+    bytes at k = 128; for the swapped square, whose honest roots the oracle
+    refuses, the blind oracle's rows, cols and root over coracle.extend's EDS
+    up to k = 128, and None above."""
     import coracle
     from celestia_da import testfactory
     if _expect["k"] != k:
@@ -236,7 +238,9 @@ def _expected(k, j, bad):
         if k <= 32:   # the oracle's own push-order verdict names the same axis and index
             with pytest.raises(coracle.PushOrderError, match=f"{'col' if want[0] else 'row'} {want[1]}$"):
                 coracle.roots(eds, k)
-        out = (ods, eds, None, None, None, want)
+        # its roots are the blind ones (BlindTree: the hashing without the order check)
+        rows, cols, root = coracle.blind_dah(eds, k, 16 if k >= 64 else 0) if k <= 128 else (None, None, None)
+        out = (ods, eds, rows, cols, root, want)
     else:
         ods = testfactory.random_square(k, j)
         if k == 128:
@@ -273,7 +277,8 @@ def test_sweep_batch_matches_oracle(ctx, k, n):
     an equal square).  Every square's EDS, row roots, column roots and data
     root equal the oracle's, compared on the device; for n >= 4 distinct
     square 2 carries a push-order violation and exactly its copies report
-    CDA_ERR_PUSH_ORDER with the brute-force detail."""
+    CDA_ERR_PUSH_ORDER with the brute-force detail (and, up to k = 128, the
+    blind oracle's roots and data root)."""
     import torch
     W = 2 * k
     d = _distinct(k, n)

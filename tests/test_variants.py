@@ -38,12 +38,17 @@ import torch
 from celestia_da import Context, testfactory
 ctx = Context(0)
 dev = torch.device("cuda", 0)
+square = testfactory.random_square
+if sys.argv[1] == "edges":   # P-left and the ladder square in turn (tests/nmt_edge_squares.py)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import nmt_edge_squares
+    square = lambda k, i: nmt_edge_squares.square(("p_left", "ladder")[i % 2], k).reshape(k * k, 512)
 sha = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
 for k, n in zip(map(int, sys.argv[2::2]), map(int, sys.argv[3::2])):
     W = 2 * k
     eds = torch.zeros(n, W * W * 512, dtype=torch.uint8, device=dev)
     for i in range(n):
-        eds[i].view(W, W, 512)[:k, :k] = torch.from_numpy(testfactory.random_square(k, i)).to(dev).view(k, k, 512)
+        eds[i].view(W, W, 512)[:k, :k] = torch.from_numpy(square(k, i)).to(dev).view(k, k, 512)
     rows = torch.empty(n, W * 90, dtype=torch.uint8, device=dev)
     cols = torch.empty(n, W * 90, dtype=torch.uint8, device=dev)
     roots = torch.empty(n, 32, dtype=torch.uint8, device=dev)
@@ -59,14 +64,16 @@ for k, n in zip(map(int, sys.argv[2::2]), map(int, sys.argv[3::2])):
 """.replace("ROOT", repr(ROOT))
 
 
-def _run_cases(env_extra: dict, cases: list) -> list:
+def _run_cases(env_extra: dict, cases: list, squares: str = "x") -> list:
     """One fresh process on the test build with `env_extra` set: the squares
-    0 .. n-1 of every (k, n) of `cases`, one in-place batch each."""
+    0 .. n-1 of every (k, n) of `cases`, one in-place batch each.  squares =
+    "edges": the edge-namespace squares of test_namespace_edges.py in place
+    of the random ones."""
     env = dict(os.environ)
     env.update(env_extra)
     env["CDA_LIB"] = knobs.lib_path_for_tests()   # the A/B knobs are read only by the test build
     args = [str(x) for kn in cases for x in kn]
-    r = subprocess.run([sys.executable, "-c", _CHILD, "x", *args], env=env, capture_output=True, text=True,
+    r = subprocess.run([sys.executable, "-c", _CHILD, squares, *args], env=env, capture_output=True, text=True,
                        timeout=180)
     assert r.returncode == 0, r.stderr[-2000:]
     return [json.loads(line) for line in r.stdout.strip().splitlines()[-len(cases):]]
