@@ -71,6 +71,7 @@ EXPORTED = (
     "cda_share_proofs_verify", "cda_square_sample_proofs", "cda_sample_proofs_verify",
     "cda_square_share_proofs_plan", "cda_square_share_proofs", "cda_square_tx_share_ranges",
     "cda_square_namespace_plan", "cda_square_namespace_proofs", "cda_namespace_proofs_verify",
+    "cda_befp_build", "cda_befp_build_device", "cda_befp_batch_check", "cda_befp_verify",
 )
 # cda_namespace_proof_batch kinds (include/cda.h)
 CDA_NAMESPACE_INCLUSION = 1
@@ -176,6 +177,14 @@ class NamespaceProofBatch(C.Structure):
                 ("absence_leaf", _u8p)]
 
 
+class BefpBatch(C.Structure):
+    """cda_befp_batch (include/cda.h)."""
+    _u8p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    _fields_ = [("n_proofs", C.c_uint32), ("k", C.c_uint32), ("axes", _u8p), ("indexes", _u32p),
+                ("row_roots", _u8p), ("col_roots", _u8p), ("share_off", _u32p), ("positions", _u32p),
+                ("proof_axes", _u8p), ("shares", _u8p), ("nmt_nodes", _u8p)]
+
+
 _lib = None
 _libs = {}
 _lock = threading.RLock()   # re-entrant: default_context() creates a Context (load()) under it
@@ -267,6 +276,11 @@ def load(path: str | None = None):
         L.cda_square_namespace_plan.argtypes = [vp, u8p, C.c_uint32, C.POINTER(NamespacePlanT)]
         L.cda_square_namespace_proofs.argtypes = [vp, u8p, C.c_uint32, C.POINTER(NamespaceProofsOut)]
         L.cda_namespace_proofs_verify.argtypes = [ctxp, C.c_uint32, u8p, C.POINTER(NamespaceProofBatch), u8p]
+        L.cda_befp_build.argtypes = [ctxp, u8p, C.c_uint32, C.c_int, C.c_uint32, u8p, u8p, u32p, u32p, u8p, u8p]
+        L.cda_befp_build_device.argtypes = [ctxp, vp, C.c_uint32, C.c_int, C.c_uint32, u8p, u8p, u32p, u32p, u8p,
+                                            u8p]
+        L.cda_befp_batch_check.argtypes = [C.POINTER(BefpBatch)]
+        L.cda_befp_verify.argtypes = [ctxp, C.POINTER(BefpBatch), u8p, u8p]
         L.cda_comm_unique_id.argtypes = [u8p]
         L.cda_comm_init.argtypes = [ctxp, C.c_int, C.c_int, u8p]
         L.cda_comm_destroy.argtypes = [ctxp]

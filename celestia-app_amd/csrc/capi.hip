@@ -695,6 +695,39 @@ int cda_rs_decode(cda_ctx* ctx, uint8_t* shards, const uint8_t* present, uint32_
     });
 }
 
+int cda_befp_build(cda_ctx* ctx, const uint8_t* eds, uint32_t w, int axis, uint32_t index, const uint8_t* row_roots,
+                   const uint8_t* col_roots, uint32_t* n_out, uint32_t* positions, uint8_t* shares,
+                   uint8_t* nmt_nodes) {
+    return guarded(ctx, [&](cda::Engine& e) -> int {
+        if (!eds || !row_roots || !col_roots || !n_out || !positions || !shares || !nmt_nodes)
+            return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.befp_build(eds, nullptr, w, axis, index, row_roots, col_roots, n_out, positions, shares, nmt_nodes);
+    });
+}
+
+int cda_befp_build_device(cda_ctx* ctx, const void* d_eds, uint32_t w, int axis, uint32_t index,
+                          const uint8_t* row_roots, const uint8_t* col_roots, uint32_t* n_out, uint32_t* positions,
+                          uint8_t* shares, uint8_t* nmt_nodes) {
+    return guarded(ctx, [&](cda::Engine& e) -> int {
+        if (!d_eds || !row_roots || !col_roots || !n_out || !positions || !shares || !nmt_nodes)
+            return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.befp_build(nullptr, static_cast<const uint8_t*>(d_eds), w, axis, index, row_roots, col_roots, n_out,
+                            positions, shares, nmt_nodes);
+    });
+}
+
+int cda_befp_batch_check(const cda_befp_batch* b) {
+    // Host-only (no device work), no context.
+    return host_only(nullptr, [&](std::string* err) -> int {
+        *err = cda::befp_batch_check(b);
+        return err->empty() ? CDA_OK : CDA_ERR_INVALID;
+    });
+}
+
+int cda_befp_verify(cda_ctx* ctx, const cda_befp_batch* b, uint8_t* verdict, uint8_t* rebuilt_roots) {
+    return guarded(ctx, [&](cda::Engine& e) -> int { return e.befp_verify(b, verdict, rebuilt_roots); });
+}
+
 int cda_nmt_axis_roots(cda_ctx* ctx, const uint8_t* cells, uint32_t cell_len, uint32_t n_cells, uint32_t n_trees,
                        uint32_t square_size, const uint32_t* axis_index, uint8_t* roots, int32_t* status) {
     return guarded(ctx, [&](cda::Engine& e) -> int {

@@ -20,6 +20,7 @@ struct cda_share_proofs_out;
 struct cda_namespace_plan_t;
 struct cda_namespace_proofs_out;
 struct cda_namespace_proof_batch;
+struct cda_befp_batch;
 namespace cda {
 class OutRegions;      // out_regions.h
 struct ResidentView;   // resident_proof_dev.h
@@ -129,6 +130,10 @@ struct GatherPiece {
     uint64_t dst;
     uint32_t len;
 };
+
+// befp.hip: the structural checks of a fraud-proof batch, host only: "" or the first malformed field's text,
+// naming the proof and the field.
+std::string befp_batch_check(const cda_befp_batch* b);
 
 // comm.hip: ncclGetUniqueId into 128 bytes (CDA_OK / CDA_ERR_DEVICE).
 int comm_unique_id(uint8_t* id);
@@ -342,6 +347,14 @@ class Engine {
     int namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const cda_namespace_proof_batch* b,
                                 uint8_t* verdict);
 
+    // Bad-encoding fraud proofs (befp.hip).  befp_build: every cell of vector (axis, index) of a host (eds) or
+    // device (d_eds) square whose orthogonal vector hashes to its DAH root, with its proof against that root;
+    // one of eds / d_eds is set.  befp_verify: BadEncodingProof.Validate of a batch (include/cda.h).
+    int befp_build(const uint8_t* eds, const uint8_t* d_eds, uint32_t w, int axis, uint32_t index,
+                   const uint8_t* row_roots, const uint8_t* col_roots, uint32_t* n_out, uint32_t* positions,
+                   uint8_t* shares, uint8_t* nmt_nodes);
+    int befp_verify(const cda_befp_batch* b, uint8_t* verdict, uint8_t* rebuilt_roots);
+
     // Stage timing with HIP events on the launch stream (bench / profiling).
     enum Stage { kStageRsQ0 = 0, kStageRsQ3, kStageOrder, kStageLeaves, kStageLevels, kStageDataRoot, kNumStages };
     void set_profiling(bool on) { profiling_ = on; }
@@ -508,6 +521,11 @@ class Engine {
     DevBuf tr_cells_, tr_levels_, tr_axis_, tr_roots_;
     // proof verification: the uploaded batch; leaf / fold node scratch, flags and verdicts
     DevBuf vp_in_, vp_scratch_;
+    // where share_proofs_verify put the last batch's shares (in vp_in_, valid until the next batch is uploaded):
+    // befp_verify scatters the verified ones from there instead of uploading them again
+    const uint8_t* vp_shares_dev_ = nullptr;
+    // fraud proofs: the builder's tree levels and outputs; the verifier's tables, vectors and results
+    DevBuf bf_levels_, bf_out_, bf_in_, bf_grid_;
     DevBuf rs_pad_;   // Codec.Encode of a non-power-of-two shard count
     // config 5 in the library: RCCL communicator (ncclComm_t), row block,
     // send buffer, column block, slots
@@ -529,6 +547,9 @@ class Engine {
     int comm_group(const char* what, const std::function<int(void*)>& post);
     int build_trees(const uint8_t* cells, uint32_t cell_len, uint32_t n_cells, uint32_t n_trees, uint32_t square_size,
                     const uint32_t* axis, std::vector<uint64_t>* level_off, std::vector<uint32_t>* err_out);
+    int build_trees_device(const uint8_t* d_cells, uint32_t cell_len, uint32_t n_cells, uint32_t n_trees,
+                           uint32_t square_size, const uint32_t* axis, uint32_t** d_err_out, hipStream_t s,
+                           uint64_t* root_off = nullptr);
     int tree_order_error(const uint8_t* cells, uint32_t cell_len, uint32_t n_cells, uint32_t square_size,
                          const uint32_t* axis, const std::vector<uint32_t>& err, int32_t* status);   // roots of the last repair_verify (rows then columns)
     int ensure_gf8_tables();

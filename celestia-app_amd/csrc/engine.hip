@@ -105,7 +105,7 @@ Engine::~Engine() {
                       &cm_leaf_, &cm_lvl_, &cm_roots_, &cm_out_, &gf8_log_, &gf8_exp_, &gf8_skew_, &rp_cw_,
                       &rp_err_, &rp_present_, &rp_parity_, &rp_buf_, &rp_flags_, &tr_cells_, &tr_levels_,
                       &tr_axis_, &tr_roots_, &rs_pad_, &split_blk_, &split_send_, &split_col_, &split_slots_,
-                      &comm_flag_, &h_par_, &vp_in_, &vp_scratch_})
+                      &comm_flag_, &h_par_, &vp_in_, &vp_scratch_, &bf_levels_, &bf_out_, &bf_in_, &bf_grid_})
         b->release();
     if (sq_event_) (void)hipEventSynchronize(sq_event_), (void)hipEventDestroy(sq_event_);
     if (sq_stage_) (void)hipHostFree(sq_stage_);

@@ -164,27 +164,48 @@ int Engine::build_trees(const uint8_t* cells, uint32_t cell_len, uint32_t n_cell
     }
     const uint64_t cells_b = (uint64_t)n_trees * n_cells * cell_len;
     CDA_TRY(ensure(tr_cells_, cells_b + 16, "hipMalloc tree cells"));
+    CDA_TRY(h2d(tr_cells_.ptr, cells, cells_b, s, "H2D"));
+    uint32_t* d_err = nullptr;
+    CDA_TRY(build_trees_device(tr_cells_.as<uint8_t>(), cell_len, n_cells, n_trees, square_size, axis, &d_err, s));
+    err_out->assign(n_trees, 0);
+    CDA_TRY(d2h(err_out->data(), d_err, (size_t)n_trees * 4, s, "D2H"));
+    return CDA_OK;
+}
+
+// The same trees over cells that already lie in device memory (befp.hip: the rebuilt vectors): every level into
+// tr_levels_ at build_trees' offsets, *d_err = one push-order word per tree (the bare push position of the first
+// violation, ~0 = ordered), in tr_axis_; *root_off (optional) = bytes into tr_levels_ of the root slots, one per
+// tree.  Enqueue only.
+int Engine::build_trees_device(const uint8_t* d_cells, uint32_t cell_len, uint32_t n_cells, uint32_t n_trees,
+                               uint32_t square_size, const uint32_t* axis, uint32_t** d_err_out, hipStream_t s,
+                               uint64_t* root_off) {
+    const std::vector<uint32_t> cnt = level_counts(n_cells);
+    std::vector<uint64_t> off(cnt.size(), 0);
+    uint64_t total = 0;
+    for (size_t L = 0; L < cnt.size(); L++) {
+        off[L] = total;
+        total += (uint64_t)cnt[L] * n_trees * kSlot;
+    }
     CDA_TRY(ensure(tr_levels_, total, "hipMalloc tree levels"));
     CDA_TRY(ensure(tr_axis_, (size_t)n_trees * 8, "hipMalloc tree axes"));
     uint32_t* d_axis = tr_axis_.as<uint32_t>();
     uint32_t* d_err = d_axis + n_trees;
-    CDA_TRY(h2d(tr_cells_.ptr, cells, cells_b, s, "H2D"));
+    *d_err_out = d_err;
+    if (root_off) *root_off = off.back();
     CDA_TRY(h2d(d_axis, axis, (size_t)n_trees * 4, s, "H2D"));
     CDA_TRY(fill(d_err, 0xFF, (size_t)n_trees * 4, s, "hipMemsetAsync"));
     uint8_t* lv = tr_levels_.as<uint8_t>();
     const uint64_t n_leaves = (uint64_t)n_trees * n_cells;
-    hipLaunchKernelGGL(gen_leaf_kernel, dim3((uint32_t)((n_leaves + 255) / 256)), dim3(256), 0, s,
-                       tr_cells_.as<uint8_t>(), cell_len, n_cells, n_trees, square_size, d_axis, lv, d_err);
+    hipLaunchKernelGGL(gen_leaf_kernel, dim3((uint32_t)((n_leaves + 255) / 256)), dim3(256), 0, s, d_cells, cell_len,
+                       n_cells, n_trees, square_size, d_axis, lv, d_err);
     CDA_TRY(launched("tree leaves"));
     for (size_t L = 1; L < cnt.size(); L++) {
         const uint64_t work = (uint64_t)n_trees * cnt[L];
         hipLaunchKernelGGL(gen_level_kernel, dim3((uint32_t)((work + 255) / 256)), dim3(256), 0, s,
-                           lv + (*level_off)[L - 1], cnt[L - 1], lv + (*level_off)[L], n_trees,
-                           (uint64_t)cnt[L - 1] * kSlot, (uint64_t)cnt[L] * kSlot);
+                           lv + off[L - 1], cnt[L - 1], lv + off[L], n_trees, (uint64_t)cnt[L - 1] * kSlot,
+                           (uint64_t)cnt[L] * kSlot);
         CDA_TRY(launched("tree level"));
     }
-    err_out->assign(n_trees, 0);
-    CDA_TRY(d2h(err_out->data(), d_err, (size_t)n_trees * 4, s, "D2H"));
     return CDA_OK;
 }
 

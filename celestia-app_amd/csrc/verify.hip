@@ -484,6 +484,7 @@ int Engine::share_proofs_verify(const cda_share_proof_batch* b, uint8_t* verdict
     v.aunt_off = reinterpret_cast<const uint32_t*>(dev(p_ao));
     v.aunts = in + p_aunts.off;
     v.shares = nmt ? in + p_sh.off : nullptr;
+    vp_shares_dev_ = v.shares;
     v.leaf_off = reinterpret_cast<const uint64_t*>(in + p_lo.off);
     v.n_shares = n_shares;
     v.buf_a = scr;

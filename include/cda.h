@@ -650,6 +650,73 @@ int cda_repair_device(cda_ctx *ctx, void *d_eds, const uint8_t *present, uint32_
 int cda_rs_decode(cda_ctx *ctx, uint8_t *shards, const uint8_t *present, uint32_t n_shards, uint32_t shard_len,
                   uint32_t n_codewords);
 
+/* ---- Bad-encoding fraud proofs ------------------------------------------------
+ * The step after CDA_ERR_BYZANTINE: the proof that row or column `index` of a
+ * committed square is not a codeword (specs/src/specs/fraud_proofs.md,
+ * networking.md "BadEncodingFraudProof", proto/types.proto:247-259; built from
+ * rsmt2d's ErrByzantineData and checked by celestia-node's
+ * BadEncodingProof.Validate, EXT).  A proof accuses (axis, index) of a square
+ * of ODS width k (W = 2k, D = log2 W) and carries m shares of that vector,
+ * k <= m <= W, each with its position p along the vector and a single-leaf NMT
+ * proof of D nodes (cda_square_sample_proofs' node order) against
+ *   the root of the orthogonal axis at p, leaf position index (proof axis =
+ *   the other axis: the normal case), or
+ *   the root of the accused axis at index, leaf position p (proof axis = the
+ *   accused one).
+ *
+ * cda_befp_build: every provable share of vector (axis, index) of `eds`
+ * (w*w*512 bytes: a whole square, or what cda_repair / cda_repair_device leave
+ * behind on CDA_ERR_BYZANTINE).  There is no presence mask: cell p is emitted
+ * if and only if the orthogonal vector through it hashes (without a push-order
+ * check) to its root in the DAH, which a vector with missing or garbage cells
+ * cannot.  positions (w), shares (w*512), nmt_nodes (w*D*90): the emitted
+ * cells, positions ascending, every proof against the orthogonal root;
+ * *n_out their count, which may be below k -- the caller decides what then.
+ * The launches do not grow with w but for the log2 w tree levels; one
+ * synchronisation per call.  _device: d_eds in HBM, complete before the call
+ * (as cda_repair_device leaves it); the other buffers stay host buffers. */
+int cda_befp_build(cda_ctx *ctx, const uint8_t *eds, uint32_t w, int axis, uint32_t index,
+                   const uint8_t *row_roots, const uint8_t *col_roots, uint32_t *n_out, uint32_t *positions,
+                   uint8_t *shares, uint8_t *nmt_nodes);
+int cda_befp_build_device(cda_ctx *ctx, const void *d_eds, uint32_t w, int axis, uint32_t index,
+                          const uint8_t *row_roots, const uint8_t *col_roots, uint32_t *n_out, uint32_t *positions,
+                          uint8_t *shares, uint8_t *nmt_nodes);
+/* A batch of fraud proofs of one ODS width (the caller groups by size), flat:
+ * proof q owns shares [share_off[q], share_off[q+1]). */
+typedef struct cda_befp_batch {
+    uint32_t n_proofs, k;
+    const uint8_t *axes;           /* n_proofs: accused axis, CDA_AXIS_ROW / CDA_AXIS_COL */
+    const uint32_t *indexes;       /* n_proofs: accused index */
+    const uint8_t *row_roots;      /* n_proofs*W*90: every proof's DAH */
+    const uint8_t *col_roots;      /* n_proofs*W*90 */
+    const uint32_t *share_off;     /* n_proofs+1 offsets into the share arrays; m = last */
+    const uint32_t *positions;     /* m: position along the accused vector, strictly ascending per proof */
+    const uint8_t *proof_axes;     /* m: the axis whose root the share's proof is against; NULL = the
+                                      orthogonal root for every share */
+    const uint8_t *shares;         /* m*512 */
+    const uint8_t *nmt_nodes;      /* m*D*90 */
+} cda_befp_batch;
+/* The structural checks, host only (no context; the text through
+ * cda_last_error(NULL), naming the proof and the field): k a power of two <=
+ * 512, axes <= 1, indexes and positions < W, positions strictly ascending
+ * within a proof, share_off starting at 0 and never decreasing. */
+int cda_befp_batch_check(const cda_befp_batch *b);
+/* BadEncodingProof.Validate of every proof against its DAH.  Runs
+ * cda_befp_batch_check first (CDA_ERR_INVALID; verdict is then left
+ * untouched).  verdict[q] (n_proofs bytes), the lowest number wins:
+ *   1  fewer than k shares;
+ *   2  a share is not included under the DAH root its proof names (the leaf
+ *      namespace, the tree and the leaf position are derived from (axis,
+ *      index, position, proof axis), never taken from the prover);
+ *   3  the vector rebuilt from the shares (Codec.Decode with every given share
+ *      as received, Codec.Encode of its k data shares, the erasured NMT root of
+ *      data || parity) has the DAH's root: no fraud;
+ *   0  it has another root, or breaks nmt's push order: the proof is valid.
+ * rebuilt_roots (n_proofs*90, may be NULL): the rebuilt root, hashed without
+ * the push-order check; zeros for proofs with verdict 1 or 2.  Host buffers;
+ * at most two synchronisations; n_proofs == 0 returns CDA_OK. */
+int cda_befp_verify(cda_ctx *ctx, const cda_befp_batch *b, uint8_t *verdict, uint8_t *rebuilt_roots);
+
 /* ---- Standalone erasured NMT trees -----------
  * wrapper.NewErasuredNamespacedMerkleTree(squareSize, axisIndex), n_cells
  * Pushes and Root() (pkg/wrapper/nmt_wrapper.go:55-124) for trees built
