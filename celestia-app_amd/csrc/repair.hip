@@ -284,6 +284,27 @@ __global__ __launch_bounds__(64) void parity_compare_kernel(const uint8_t* __res
     if (__any(diff) && threadIdx.x == 0) atomicOr(&flags[v], 1u);
 }
 
+// Push order of every row (blockIdx.x < k) and column with index < k: nmt
+// refuses a leaf whose namespace is below the last one pushed.  Only the Q0
+// half decides: the cells k..2k-1 of these vectors, and every cell of the
+// others, are pushed under the parity namespace, the largest there is.
+// flags[axis * W + i] |= 2 when two neighbouring Q0 cells descend.
+__global__ __launch_bounds__(64) void order_kernel(const uint8_t* __restrict__ eds, uint32_t k,
+                                                   uint32_t* __restrict__ flags) {
+    const uint32_t W = 2 * k, axis = blockIdx.x / k, i = blockIdx.x % k;
+    bool desc = false;
+    for (uint32_t p = 1 + threadIdx.x; p < k; p += 64) {
+        const size_t a = axis == 0 ? (size_t)i * W + p - 1 : (size_t)(p - 1) * W + i;
+        const size_t b = axis == 0 ? (size_t)i * W + p : (size_t)p * W + i;
+        const uint8_t* x = eds + a * kShare;
+        const uint8_t* y = eds + b * kShare;
+        int c = 0;
+        for (int q = 0; q < kNs && c == 0; q++) c = (int)y[q] - (int)x[q];
+        desc |= c < 0;
+    }
+    if (__any(desc) && threadIdx.x == 0) atomicOr(&flags[axis * W + i], 2u);
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -380,10 +401,13 @@ std::string hex(const uint8_t* p, size_t n) {
 
 // Verification of the device EDS E against the DAH (used by the sanity
 // check, after the batched sweeps and by the exact replay): the roots of
-// every row and column (one enqueue_dah) and the parity of every row and
-// column re-encoded from its data half and compared on the device.
-// bad[axis * W + i]: bit 0 = root differs, bit 1 = parity differs;
-// meaningful for complete vectors only.
+// every row and column (one enqueue_dah), the parity of every row and
+// column re-encoded from its data half and compared on the device, and the
+// push order of every row and column (order_kernel).  enqueue_dah hashes
+// blind trees and its first-violation word is per square, so the roots alone
+// cannot tell which vector nmt would have refused.
+// bad[axis * W + i]: bit 0 = root differs, bit 1 = parity differs, bit 2 =
+// namespaces descend; meaningful for complete vectors only.
 int Engine::repair_verify(const uint8_t* E, uint32_t k, const uint8_t* row_roots, const uint8_t* col_roots,
                           std::vector<uint8_t>& bad, hipStream_t s) {
     const uint32_t W = 2 * k, SH = kShare;
@@ -403,6 +427,8 @@ int Engine::repair_verify(const uint8_t* E, uint32_t k, const uint8_t* row_roots
     hipLaunchKernelGGL(parity_compare_kernel, dim3(2 * W, k), dim3(64), 0, s, E, rp_parity_.as<uint8_t>(), k,
                        rp_flags_.as<uint32_t>());
     CDA_TRY(launched("parity compare"));
+    hipLaunchKernelGGL(order_kernel, dim3(2 * k), dim3(64), 0, s, E, k, rp_flags_.as<uint32_t>());
+    CDA_TRY(launched("push order"));
     // results land in pinned memory: the copies queue right behind the
     // kernels (a pageable destination makes each copy wait for the stream and
     // go through a staging blit)
@@ -428,7 +454,7 @@ int Engine::repair_verify(const uint8_t* E, uint32_t k, const uint8_t* row_roots
         const uint8_t* got = axis == 0 ? rows.data() : cols.data();
         for (uint32_t i = 0; i < W; i++)
             bad[axis * W + i] = (std::memcmp(want + (size_t)i * kNode, got + (size_t)i * kNode, kNode) ? 1 : 0) |
-                                (flags[axis * W + i] ? 2 : 0);
+                                (flags[axis * W + i] & 1 ? 2 : 0) | (flags[axis * W + i] & 2 ? 4 : 0);
     }
     rp_roots_.assign(rows.begin(), rows.end());
     rp_roots_.insert(rp_roots_.end(), cols.begin(), cols.end());
@@ -446,12 +472,18 @@ int Engine::repair_verify(const uint8_t* E, uint32_t k, const uint8_t* row_roots
 // cells" (unique, so the reference's row/column interleaving reaches the
 // same one), then one verification of every complete vector (which covers
 // the reference's pre-repair sanity check: see precheck).  When all of
-// them match their roots and are codewords, each decode the reference would
-// have run saw cells of that same codeword, so its result and its checks are
-// the ones of the fast path (MDS uniqueness, by induction over its order).
+// them match their roots, are codewords and are in push order, each decode
+// the reference would have run saw cells of that same codeword, so its result
+// and its checks are the ones of the fast path (MDS uniqueness, by induction
+// over its order): the vector it rebuilt, and every vector it completed, is
+// complete at the fixed point with the same cells, where root, parity and
+// order were all found good.  The order verdict is needed beside the root:
+// the roots are blind ones, so a square committed over blind trees matches
+// them with a descending row, which the reference cannot push.
 // Otherwise the crossword is replayed from the input in the reference's
-// order (for i: row i, column i) with the checks after every decode, which
-// names the same first byzantine vector as rsmt2d.
+// order (for i: row i, column i) with the checks after every decode (order
+// and root of the rebuilt vector; order, root and parity of the vectors it
+// completed), which names the same first byzantine vector as rsmt2d.
 int Engine::host_repair(uint8_t* eds, const uint8_t* present_in, uint32_t W, const uint8_t* row_roots,
                         const uint8_t* col_roots, int32_t* byz_axis, uint32_t* byz_index) {
     return repair(eds, nullptr, present_in, W, row_roots, col_roots, byz_axis, byz_index);
@@ -525,19 +557,21 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
         return r == code ? code : r;
     };
     std::vector<uint8_t> bad;
-    // ---- preRepairSanityCheck: every complete vector must match its root
-    // ("bad root input", a plain error) and re-encode to its parity
+    // ---- preRepairSanityCheck: every complete vector must be in push order
+    // (ErrByzantineData: the project's choice), match
+    // its root ("bad root input", a plain error) and re-encode to its parity
     // (ErrByzantineData).  rsmt2d runs these checks in parallel goroutines;
-    // the first failure in (index, row before column, root before parity)
-    // order is reported here.  Run only on the error path: a vector complete
-    // in the input keeps its cells through the sweeps, so a clean final
-    // verification implies this check passed.
+    // the first failure in (index, row before column, order and root before
+    // parity) order is reported here.  Run only on the error path: a vector
+    // complete in the input keeps its cells through the sweeps, so a clean
+    // final verification implies this check passed.
     auto precheck = [&]() -> int {
         CDA_TRY(repair_verify(E, k, row_roots, col_roots, bad, s));
         for (uint32_t i = 0; i < W; i++)
             for (uint32_t axis = 0; axis < 2; axis++) {
                 if (count(axis, i) != W) continue;
                 const uint8_t b = bad[axis * W + i];
+                if (b & 4) return byzantine(axis, i);   // nmt cannot push it: no root to compare
                 if (b & 1) {
                     char head[64];
                     snprintf(head, sizeof head, "bad root input: %s %u expected ", axis == 0 ? "row" : "col", i);
@@ -603,9 +637,9 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
                 for (uint32_t p = 0; p < W; p++) present[cell(axis, i, p)] = 1;
                 progress = true;
                 CDA_TRY(repair_verify(E, k, row_roots, col_roots, bad, s));
-                // the rebuilt vector against its root, then the orthogonal
-                // vectors it completed against their roots and encodings
-                if (bad[axis * W + i] & 1) return byzantine(axis, i);
+                // the rebuilt vector's push order and root, then the
+                // orthogonal vectors it completed: order, root and encoding
+                if (bad[axis * W + i] & 5) return byzantine(axis, i);
                 for (uint32_t o = 0; o < W; o++)
                     if (was[o] && bad[ox * W + o]) return byzantine(ox, o);
             }

@@ -634,7 +634,10 @@ int cda_namespace_proofs_verify(cda_ctx *ctx, uint32_t k, const uint8_t *row_roo
  * reconstructed).  row_roots / col_roots: w*90 bytes each (the DAH).
  * Returns CDA_OK (eds complete), CDA_ERR_BYZANTINE (*byz_axis 0 row / 1 col,
  * *byz_index), CDA_ERR_UNREPAIRABLE, or CDA_ERR_INVALID for a complete vector
- * whose root differs from the given one ("bad root input: ..."). */
+ * whose root differs from the given one ("bad root input: ...").  The roots
+ * are compared as blind ones (no push-order check); a row or column whose Q0
+ * namespaces descend is CDA_ERR_BYZANTINE whatever its root is, when rebuilt,
+ * when completed by a rebuild, and also when complete in the input. */
 int cda_repair(cda_ctx *ctx, uint8_t *eds, const uint8_t *present, uint32_t w, const uint8_t *row_roots,
                const uint8_t *col_roots, int32_t *byz_axis, uint32_t *byz_index);
 /* cda_repair on an HBM-resident square (d_eds: w*w*512 device bytes, repaired

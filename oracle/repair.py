@@ -14,7 +14,9 @@ Restates (EXT modules, not vendored in /root/reference; pins go.mod:11,13):
   shard i is i (m = number of parity shards = k).
 * celestiaorg/rsmt2d v0.14.0 ``ExtendedDataSquare.Repair``:
   preRepairSanityCheck (complete rows / columns must match their roots and
-  their parity must re-encode) followed by solveCrossword, which loops
+  their parity must re-encode; one that breaks nmt's push order is
+  ErrByzantineData here, a choice of this project: see repair()) followed by
+  solveCrossword, which loops
   ``for i: solveCrosswordRow(i); solveCrosswordCol(i)`` until solved or no
   progress (ErrUnrepairableDataSquare).  A rebuilt vector whose root
   differs, or an orthogonal vector it completes whose root or encoding
@@ -35,9 +37,13 @@ ROW, COL = 0, 1
 
 
 class ErrByzantineData(Exception):
-    def __init__(self, axis: int, index: int):
+    def __init__(self, axis: int, index: int, how: str = ""):
         super().__init__(f"byzantine {'row' if axis == ROW else 'col'}: {index}")
         self.axis, self.index = axis, index
+        # which check named the vector (for the tests' coverage conditions; rsmt2d's error has no such field):
+        # "check-order" / "check-parity" (pre-repair check), "rebuilt-order" / "rebuilt-root",
+        # "orth-order" / "orth-root" / "orth-parity" (a vector the rebuild completed)
+        self.how = how
 
 
 class ErrUnrepairableDataSquare(Exception):
@@ -170,16 +176,23 @@ def repair(eds: np.ndarray, present: np.ndarray, row_roots, col_roots) -> np.nda
         v = vec(axis, i)
         return np.array_equal(pyref.leopard_encode(v[:k]), v[k:])
 
-    # preRepairSanityCheck
+    # preRepairSanityCheck.  A complete vector whose namespaces descend cannot
+    # be pushed into its tree at all; rsmt2d's handling of that error here is
+    # not pinned by any source at hand, so this is the project's choice: the
+    # same ErrByzantineData that solve() gives a rebuilt unordered vector,
+    # for the first such vector in the check's order.
     for i in range(W):
         for axis in (ROW, COL):
             if pres(axis, i).all():
-                got = root(axis, i)
+                try:
+                    got = root(axis, i)
+                except pyref.PushOrderError:
+                    raise ErrByzantineData(axis, i, "check-order")
                 if got != want(axis, i):
                     raise ErrBadRoot(f"bad root input: {'row' if axis == ROW else 'col'} {i} expected "
                                      f"{want(axis, i).hex()} got {got.hex()}")
                 if not encoding_ok(axis, i):
-                    raise ErrByzantineData(axis, i)
+                    raise ErrByzantineData(axis, i, "check-parity")
 
     def solve(axis, i):
         p = pres(axis, i)
@@ -191,9 +204,9 @@ def repair(eds: np.ndarray, present: np.ndarray, row_roots, col_roots) -> np.nda
         try:
             got = pyref.axis_root(rebuilt, k, i)
         except pyref.PushOrderError:
-            raise ErrByzantineData(axis, i)
+            raise ErrByzantineData(axis, i, "rebuilt-order")
         if got != want(axis, i):
-            raise ErrByzantineData(axis, i)
+            raise ErrByzantineData(axis, i, "rebuilt-root")
         ox = COL if axis == ROW else ROW
         newly = np.nonzero(~p)[0]
         # orthogonal vectors this rebuild completes
@@ -206,9 +219,11 @@ def repair(eds: np.ndarray, present: np.ndarray, row_roots, col_roots) -> np.nda
                 try:
                     ogot = pyref.axis_root(ov, k, o)
                 except pyref.PushOrderError:
-                    raise ErrByzantineData(ox, o)
-                if ogot != want(ox, o) or not np.array_equal(pyref.leopard_encode(ov[:k]), ov[k:]):
-                    raise ErrByzantineData(ox, o)
+                    raise ErrByzantineData(ox, o, "orth-order")
+                if ogot != want(ox, o):
+                    raise ErrByzantineData(ox, o, "orth-root")
+                if not np.array_equal(pyref.leopard_encode(ov[:k]), ov[k:]):
+                    raise ErrByzantineData(ox, o, "orth-parity")
         if axis == ROW:
             eds[i] = rebuilt
             present[i] = True

@@ -108,11 +108,17 @@ def flipped_cell(k: int):
     return (k - 1, k) if k > 1 else (0, 1)
 
 
+def flipped_cells(k: int):
+    """Two cells per quadrant, Q0..Q3: the corners of the square and the cells about its centre."""
+    W = 2 * k
+    return [(0, 0), (k - 1, k - 1), (0, W - 1), (k - 1, k), (W - 1, 0), (k, k - 1), (k, k), (W - 1, W - 1)]
+
+
 @functools.lru_cache(maxsize=None)
-def malicious_square(k: int) -> Square:
-    """The honest EDS with a few bytes of one Q1 cell flipped and all 4k roots recomputed from the corrupted
-    cells: row r and column c are committed non-codewords."""
-    r, c = flipped_cell(k)
+def malicious_square(k: int, cell=None) -> Square:
+    """The honest EDS with a few payload bytes of one cell flipped (`cell`, default the Q1 cell flipped_cell(k))
+    and all 4k roots recomputed from the corrupted cells: row r and column c are committed non-codewords."""
+    r, c = flipped_cell(k) if cell is None else cell
     eds = honest_square(k).eds.copy()
     eds[r, c, 100:104] ^= 0x5A
     return committed(eds)

@@ -14,7 +14,12 @@ Checks:
     square, and for byzantine / unrepairable / bad-root inputs the same
     outcome as the oracle's replay in the reference's visiting order
     (axis and index of the byzantine vector included).  k=512 is checked by
-    the erase -> repair round trip (size-independent property).
+    the erase -> repair round trip (size-independent property);
+  * GPU, decode sweep: every mask of k = 1, 2, 4 and every exactly-k mask of
+    k = 8 in one call each, complete codewords between incomplete ones, and
+    GF(2^16) with two 64-byte blocks per shard.
+
+Maliciously committed and unordered squares: tests/test_repair_malicious.py.
 """
 import gzip
 import os
@@ -55,14 +60,20 @@ def erasure_patterns(k, rng):
     return pats
 
 
-def run_oracle(eds, present, rows, cols):
+def run_oracle(eds, present, rows, cols, info=None):
+    """info (a dict, optional) receives what the outcome alone does not say: "error", the text of a bad-root
+    error, and "how", the check that named a byzantine vector."""
     try:
         return "ok", orp.repair(np.where(present[..., None], eds, 0), present, rows, cols)
     except orp.ErrByzantineData as e:
+        if info is not None:
+            info["how"] = e.how
         return ("byz", e.axis, e.index), None
     except orp.ErrUnrepairableDataSquare:
         return "unrep", None
-    except orp.ErrBadRoot:
+    except orp.ErrBadRoot as e:
+        if info is not None:
+            info["error"] = str(e)
         return "badroot", None
 
 
@@ -147,11 +158,15 @@ def test_codec_decode_api(ctx):
         codec.decode([full[0]] + [None] * 15)
 
 
-def gpu_repair(ctx, eds, present, rows, cols):
+def gpu_repair(ctx, eds, present, rows, cols, info=None):
+    """cda_repair through the rsmt2d wrapper.  info (a dict, optional) receives "square", the square as the call
+    left it whatever the outcome, and "error", the whole text of a bad-root error."""
     from celestia_da import ByzantineDataError, CdaError, UnrepairableError, rsmt2d, wrapper
     W = eds.shape[0]
     sq = rsmt2d.new_extended_data_square_with_missing(eds, present, rsmt2d.LeoRSCodec(ctx),
                                                      wrapper.new_constructor(W // 2))
+    if info is not None:
+        info["square"] = sq.array()   # repaired in place
     try:
         sq.repair(rows, cols, present)
         return "ok", sq.array()
@@ -161,6 +176,8 @@ def gpu_repair(ctx, eds, present, rows, cols):
         return "unrep", None
     except CdaError as e:
         assert "bad root input" in str(e)
+        if info is not None:
+            info["error"] = str(e)
         return "badroot", None
 
 
@@ -256,8 +273,8 @@ def test_repair_k512_round_trip(ctx):
     assert np.array_equal(rep, sq.array())
 
 
-def device_repair(ctx, eds, present, rows, cols):
-    """cda_repair_device on an HBM-resident copy of the square."""
+def device_repair(ctx, eds, present, rows, cols, info=None):
+    """cda_repair_device on an HBM-resident copy of the square; info as for gpu_repair."""
     import ctypes as C
 
     import torch
@@ -272,6 +289,8 @@ def device_repair(ctx, eds, present, rows, cols):
     ax, ix = C.c_int32(-1), C.c_uint32(0)
     rc = ctx.lib.cda_repair_device(ctx.h, d.data_ptr(), ptr(p), W, ptr(rb), ptr(cb), C.byref(ax), C.byref(ix))
     out = d.cpu().numpy().reshape(W, W, 512)
+    if info is not None:
+        info["square"] = out
     if rc == 0:
         return "ok", out
     if rc == -9:
@@ -279,6 +298,8 @@ def device_repair(ctx, eds, present, rows, cols):
     if rc == -10:
         return "unrep", None
     assert rc == -6 and "bad root input" in ctx.lib.cda_last_error(ctx.h).decode()
+    if info is not None:
+        info["error"] = ctx.lib.cda_last_error(ctx.h).decode()
     return "badroot", None
 
 
@@ -311,3 +332,93 @@ def test_repair_device_matches_host(ctx, k):
         assert h[0] == d[0], (i, h[0], d[0])
         if h[0] == "ok":
             assert np.array_equal(h[1], d[1]) and np.array_equal(d[1], eds)
+
+
+# ------------------------------------------------------------------ GPU: decode sweep
+# The expected value is the original codeword (coracle.leopard_encode): the code is MDS, so the decoded
+# symbols are unique.  Complete codewords, which the engine skips, sit between incomplete ones, so the
+# decode kernels' codeword list is not the identity.
+def sweep_codewords(k, L, n_distinct, seed):
+    """(n_distinct, 2k, L): random data, but codeword 0 all-zero data and codeword 1 all-0xFF data."""
+    rng = np.random.default_rng(seed)
+    data = rng.integers(0, 256, (n_distinct, k, L), dtype=np.uint8)
+    data[0] = 0
+    data[1] = 0xFF
+    return np.stack([np.concatenate([d, coracle.leopard_encode(d)]) for d in data])
+
+
+def decode_and_compare(ctx, cws, pres):
+    from celestia_da import rsmt2d
+    shards = np.where(pres[..., None], cws, 0).astype(np.uint8)
+    rsmt2d.LeoRSCodec(ctx).decode_batch(shards, pres)
+    wrong = np.nonzero((shards != cws).any(axis=(1, 2)))[0]
+    assert wrong.size == 0, (wrong[:8].tolist(), pres[wrong[:8]].astype(int).tolist())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [1, 2, 4])
+def test_rs_decode_every_mask(ctx, k):
+    """Every mask with at least k of the 2k shards present, the complete one included, in one call."""
+    n = 2 * k
+    masks = np.array([[(m >> p) & 1 for p in range(n)] for m in range(1 << n)], dtype=bool)
+    masks = masks[masks.sum(axis=1) >= k]
+    assert len(masks) == {1: 3, 2: 11, 4: 163}[k] and masks[-1].all() and masks[:-1].all(axis=1).sum() == 0
+    masks = np.roll(masks, len(masks) // 2, axis=0)   # the complete codeword in the middle of the batch
+    distinct = sweep_codewords(k, 64, 16, 500 + k)
+    decode_and_compare(ctx, distinct[np.arange(len(masks)) % 16], masks)
+
+
+@pytest.mark.gpu
+def test_rs_decode_every_mask_of_k_present_k8(ctx):
+    """k = 8: all C(16, 8) = 12 870 masks with exactly 8 shards present, in one call, over 16 distinct
+    codewords (one of all-zero, one of all-0xFF data)."""
+    import itertools
+    k, n = 8, 16
+    combos = np.array(list(itertools.combinations(range(n), k)))
+    assert combos.shape == (12870, k)
+    masks = np.zeros((len(combos), n), dtype=bool)
+    masks[np.arange(len(combos))[:, None], combos] = True
+    distinct = sweep_codewords(k, 64, 16, 508)
+    assert not distinct[0].any() and (distinct[1][:k] == 0xFF).all()
+    decode_and_compare(ctx, distinct[np.arange(len(masks)) % 16], masks)
+
+
+def gf16_masks(k, rng):
+    n = 2 * k
+    lost = []
+    lost.append(np.arange(0, k))                      # first k lost
+    lost.append(np.arange(k, n))                      # last k lost
+    lost.append(np.arange(k // 2, k // 2 + k))        # a run of k straddling the data / parity boundary
+    lost.append(np.arange(0, n, 2))                   # every other shard lost
+    lost.append(np.array([], dtype=np.int64))         # complete, in the middle of the batch
+    lost.append(np.array([k + 1]))                    # one shard lost
+    lost.append(rng.choice(n, k, replace=False))      # two random masks with exactly k present
+    lost.append(rng.choice(n, k, replace=False))
+    masks = np.ones((len(lost), n), dtype=bool)
+    for i, e in enumerate(lost):
+        masks[i, e] = False
+    return masks
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [256, 512])
+def test_rs_decode_gf16_two_blocks(ctx, k):
+    """GF(2^16) with L = 128: two 64-byte blocks per shard, so two workgroups per codeword."""
+    rng = np.random.default_rng(600 + k)
+    masks = gf16_masks(k, rng)
+    assert masks[4].all() and (masks.sum(axis=1) >= k).all()
+    decode_and_compare(ctx, sweep_codewords(k, 128, len(masks), 700 + k), masks)
+
+
+@pytest.mark.gpu
+def test_rs_decode_present_is_any_nonzero_byte(ctx):
+    """cda_rs_decode: a shard is held when its present byte is non-zero, whatever the value."""
+    from celestia_da._lib import ptr
+    k, L = 4, 64
+    cws = sweep_codewords(k, L, 3, 800)
+    pres = np.array([[2, 0, 255, 0, 0, 1, 0, 255],
+                     [255, 255, 2, 2, 1, 1, 128, 3],
+                     [0, 0, 0, 0, 2, 255, 2, 255]], dtype=np.uint8)
+    shards = np.where((pres != 0)[..., None], cws, 0).astype(np.uint8)
+    ctx.check(ctx.lib.cda_rs_decode(ctx.h, ptr(shards), ptr(pres), k, L, 3))
+    assert np.array_equal(shards, cws)
