@@ -72,6 +72,7 @@ EXPORTED = (
     "cda_square_share_proofs_plan", "cda_square_share_proofs", "cda_square_tx_share_ranges",
     "cda_square_namespace_plan", "cda_square_namespace_proofs", "cda_namespace_proofs_verify",
     "cda_befp_build", "cda_befp_build_device", "cda_befp_batch_check", "cda_befp_verify",
+    "cda_square_commitment_proofs_plan", "cda_square_commitment_proofs", "cda_commitment_proofs_verify",
 )
 # cda_namespace_proof_batch kinds (include/cda.h)
 CDA_NAMESPACE_INCLUSION = 1
@@ -79,7 +80,8 @@ CDA_NAMESPACE_ABSENCE = 2
 # cda_square_sample_proofs axes (include/cda.h)
 CDA_AXIS_ROW = 0
 CDA_AXIS_COL = 1
-STAGES = ("rs_q0", "rs_q3", "order_check", "nmt_leaves", "nmt_levels", "data_root")
+STAGES = ("rs_q0", "rs_q3", "order_check", "nmt_leaves", "nmt_levels", "data_root", "commitment_proofs",
+          "commitment_proofs_verify")
 
 
 class CdaError(RuntimeError):
@@ -150,6 +152,36 @@ class ShareProofsOut(C.Structure):
                 ("nodes", _u8p), ("row_roots", _u8p), ("rfc_total", _i64p), ("rfc_index", _i64p),
                 ("rfc_leaf_hash", _u8p), ("aunt_off", _u32p), ("aunts", _u8p), ("shares", _u8p),
                 ("namespaces", _u8p), ("start_row", _u32p), ("end_row", _u32p), ("one_namespace", _u8p)]
+
+
+class CommitmentProofsPlanT(C.Structure):
+    """cda_commitment_proofs_plan_t (include/cda.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("n_segments", "n_roots", "n_nodes", "n_aunts", "aunts_per_segment")]
+
+
+class CommitmentProofsOut(C.Structure):
+    """cda_commitment_proofs_out (include/cda.h)."""
+    _u8p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    _i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    _fields_ = [("seg_off", _u32p), ("nmt_start", _i32p), ("nmt_end", _i32p), ("node_off", _u32p),
+                ("nodes", _u8p), ("row_roots", _u8p), ("rfc_total", _i64p), ("rfc_index", _i64p),
+                ("rfc_leaf_hash", _u8p), ("aunt_off", _u32p), ("aunts", _u8p), ("namespaces", _u8p),
+                ("start_row", _u32p), ("end_row", _u32p), ("root_off", _u32p), ("subtree_roots", _u8p),
+                ("norm_start", _u32p), ("commitments", _u8p)]
+
+
+class CommitmentProofBatch(C.Structure):
+    """cda_commitment_proof_batch (include/cda.h)."""
+    _u8p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+    _i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+    _fields_ = [("n_proofs", C.c_uint32), ("ns_len", C.c_uint32), ("threshold", C.c_uint32),
+                ("data_roots", _u8p), ("commitments", _u8p), ("seg_off", _u32p),
+                ("nmt_start", _i32p), ("nmt_end", _i32p),
+                ("node_off", _u32p), ("nodes", _u8p), ("n_nodes", C.c_uint32),
+                ("root_off", _u32p), ("subtree_roots", _u8p), ("n_roots", C.c_uint32),
+                ("row_roots", _u8p),
+                ("rfc_total", _i64p), ("rfc_index", _i64p), ("rfc_leaf_hash", _u8p),
+                ("aunt_off", _u32p), ("aunts", _u8p), ("n_aunts", C.c_uint32)]
 
 
 class NamespacePlanT(C.Structure):
@@ -273,6 +305,11 @@ def load(path: str | None = None):
                                                u8p, u8p, u8p]
         L.cda_square_share_proofs_plan.argtypes = [C.c_uint32, u32p, u32p, C.c_uint32, C.POINTER(ShareProofsPlanT)]
         L.cda_square_share_proofs.argtypes = [vp, u32p, u32p, C.c_uint32, C.POINTER(ShareProofsOut)]
+        L.cda_square_commitment_proofs_plan.argtypes = [C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint32,
+                                                        C.POINTER(CommitmentProofsPlanT)]
+        L.cda_square_commitment_proofs.argtypes = [vp, u32p, u32p, C.c_uint32, C.c_uint32,
+                                                   C.POINTER(CommitmentProofsOut)]
+        L.cda_commitment_proofs_verify.argtypes = [ctxp, C.POINTER(CommitmentProofBatch), u8p]
         L.cda_square_namespace_plan.argtypes = [vp, u8p, C.c_uint32, C.POINTER(NamespacePlanT)]
         L.cda_square_namespace_proofs.argtypes = [vp, u8p, C.c_uint32, C.POINTER(NamespaceProofsOut)]
         L.cda_namespace_proofs_verify.argtypes = [ctxp, C.c_uint32, u8p, C.POINTER(NamespaceProofBatch), u8p]

@@ -253,6 +253,22 @@ class ResidentSquare:
         b = out.tobytes()
         return [b[32 * i:32 * (i + 1)] for i in range(n)]
 
+    def commitment_proofs(self, starts, share_lens, subtree_root_threshold: int = 64, out=None):
+        """The blob commitment proof of every blob (start, share_len) in one
+        cda_square_commitment_proofs call (one launch, one more for the
+        commitments): a CommitmentProofsBatch.  out: a
+        CommitmentProofsBatch.empty(k, starts, share_lens, threshold) to fill."""
+        st, ln = _u32_array(starts, "start"), _u32_array(share_lens, "share_len")
+        if len(st) != len(ln):
+            raise ValueError(f"{len(st)} starts but {len(ln)} share_lens")
+        if out is None:
+            out = CommitmentProofsBatch.empty(self.k, st, ln, subtree_root_threshold)
+        u32p = C.POINTER(C.c_uint32)
+        o = out.out_struct()
+        self.ctx.check(self.ctx.lib.cda_square_commitment_proofs(self.h, st.ctypes.data_as(u32p), ln.ctypes.data_as(u32p),
+                                                                 len(st), subtree_root_threshold, C.byref(o)))
+        return out
+
     def subtree_root(self, row: int, walk) -> bytes:
         """EDSSubTreeRootCacher.getSubTreeRoot (pkg/inclusion/nmt_caching.go:111-124):
         the node of EDS row tree `row` reached by `walk` (False = WalkLeft,
@@ -400,6 +416,273 @@ class ShareProofsBatch:
                                   row_proof=RowProof(cut(rb, segs.start, segs.stop, NMT_ROOT_SIZE), rp, r0[i], r1[i]),
                                   namespace_version=ns[0]))
         return out
+
+
+# ------------------------------------------------- blob inclusion by share commitment
+ERR_NOT_A_BLOB = "commitment proof is not one contiguous blob"
+ERR_SUBTREE_ROOTS = "subtree roots failed to verify against the row roots"
+ERR_COMMITMENT = "subtree roots do not hash to the share commitment"
+# cda_commitment_proofs_verify's verdicts (include/cda.h); the numbering is this library's choice
+COMMITMENT_VERDICT_TEXT = {0: None, 1: ERR_ROW_PROOF, 2: ERR_SUBTREE_ROOTS, 3: ERR_COMMITMENT, 4: ERR_NOT_A_BLOB}
+
+
+def _u32_array(values, what: str) -> np.ndarray:
+    a = np.asarray(values, dtype=np.int64).reshape(-1)
+    if a.size and (a.min() < 0 or a.max() >= 1 << 32):
+        raise _lib.CdaError(_lib.CDA_ERR_INVALID, f"{what} does not fit 32 bits")
+    return np.ascontiguousarray(a.astype(np.uint32))
+
+
+def commitment_proofs_plan(k: int, starts, share_lens, subtree_root_threshold: int = 64) -> dict:
+    """cda_square_commitment_proofs_plan: n_segments, n_roots, n_nodes,
+    n_aunts, aunts_per_segment of the batch of blobs (start, share_len) of a
+    square of ODS width k.  Host only, no context; CdaError names the blob and
+    the field."""
+    st, ln = _u32_array(starts, "start"), _u32_array(share_lens, "share_len")
+    if len(st) != len(ln):
+        raise ValueError(f"{len(st)} starts but {len(ln)} share_lens")
+    L = _lib.load()
+    u32p = C.POINTER(C.c_uint32)
+    p = _lib.CommitmentProofsPlanT()
+    rc = L.cda_square_commitment_proofs_plan(k, st.ctypes.data_as(u32p), ln.ctypes.data_as(u32p), len(st),
+                                             subtree_root_threshold, C.byref(p))
+    if rc != _lib.CDA_OK:
+        raise _lib.CdaError(rc, L.cda_last_error(None).decode())
+    return {n: getattr(p, n) for n, _ in _lib.CommitmentProofsPlanT._fields_}
+
+
+@dataclass
+class CommitmentProof:              # celestia-node blob.CommitmentProof
+    subtree_roots: list             # 90 bytes each, row by row, left to right
+    subtree_root_proofs: list       # one NMTProof per row: the nodes of ProveRange(start, end)
+    namespace: bytes                # 29 bytes
+    row_proof: RowProof
+
+    @property
+    def share_len(self) -> int:
+        """The blob's share count: the sum of the rows' ranges."""
+        return sum(p.end - p.start for p in self.subtree_root_proofs)
+
+    def validate(self, data_root: bytes, commitment: bytes, subtree_root_threshold: int = 64, ctx=None):
+        """None when the blob with share commitment `commitment` lies in the
+        square with `data_root`, else the verdict's text."""
+        return validate_commitment_proofs([self], [data_root], [commitment], subtree_root_threshold, ctx)[0]
+
+
+class CommitmentProofsBatch:
+    """The commitment proofs of n blobs of one square as the flat arrays of
+    cda_commitment_proofs_out (numpy; include/cda.h): proof i owns the
+    segments (rows) seg_off[i] .. seg_off[i + 1], segment g the subtree roots
+    root_off[g] .. root_off[g + 1], the nodes node_off[g] .. node_off[g + 1]
+    and the aunts aunt_off[g] .. aunt_off[g + 1]."""
+
+    FIELDS = tuple(n for n, _ in _lib.CommitmentProofsOut._fields_)
+
+    def __init__(self, k, starts, share_lens, threshold, **arrays):
+        self.k, self.starts, self.share_lens, self.threshold = k, starts, share_lens, threshold
+        for name in self.FIELDS:
+            setattr(self, name, arrays[name])
+
+    @classmethod
+    def empty(cls, k, starts, share_lens, threshold: int = 64, fill=None):
+        """Buffers of the plan's sizes (filled with the byte `fill` if given)."""
+        st, ln = _u32_array(starts, "start"), _u32_array(share_lens, "share_len")
+        p = commitment_proofs_plan(k, st, ln, threshold)
+        n, S = len(st), p["n_segments"]
+        shapes = {"seg_off": ((n + 1,), np.uint32), "nmt_start": ((S,), np.int32), "nmt_end": ((S,), np.int32),
+                  "node_off": ((S + 1,), np.uint32), "nodes": ((p["n_nodes"], NMT_ROOT_SIZE), np.uint8),
+                  "row_roots": ((S, NMT_ROOT_SIZE), np.uint8), "rfc_total": ((S,), np.int64),
+                  "rfc_index": ((S,), np.int64), "rfc_leaf_hash": ((S, 32), np.uint8),
+                  "aunt_off": ((S + 1,), np.uint32), "aunts": ((p["n_aunts"], 32), np.uint8),
+                  "namespaces": ((n, 29), np.uint8), "start_row": ((n,), np.uint32), "end_row": ((n,), np.uint32),
+                  "root_off": ((S + 1,), np.uint32), "subtree_roots": ((p["n_roots"], NMT_ROOT_SIZE), np.uint8),
+                  "norm_start": ((n,), np.uint32), "commitments": ((n, 32), np.uint8)}
+        arrays = {}
+        for name, (shape, dtype) in shapes.items():
+            a = np.empty(shape, dtype=dtype)
+            if fill is not None:
+                a.view(np.uint8).fill(fill)
+            arrays[name] = a
+        return cls(k, st, ln, threshold, **arrays)
+
+    def __len__(self):
+        return len(self.starts)
+
+    def arrays(self):
+        return tuple(getattr(self, name) for name in self.FIELDS)
+
+    def out_struct(self, skip=()):
+        """cda_commitment_proofs_out over the arrays (NULL for the names in `skip`)."""
+        o = _lib.CommitmentProofsOut()
+        for (name, t), a in zip(_lib.CommitmentProofsOut._fields_, self.arrays()):
+            if name not in skip:
+                setattr(o, name, a.ctypes.data_as(t))
+        return o
+
+    def batch(self, data_root, commitments=None):
+        """The cda_commitment_proof_batch over these arrays, unchanged: pointer
+        assignment.  data_root: 32 bytes for every proof, or n * 32;
+        commitments: n * 32 claimed commitments (None: the batch's own)."""
+        n = len(self)
+        roots = np.frombuffer(bytes(data_root), dtype=np.uint8) if isinstance(data_root, (bytes, bytearray)) \
+            else np.ascontiguousarray(data_root, dtype=np.uint8).reshape(-1)
+        if roots.size == 32:
+            roots = np.tile(roots, max(1, n))
+        if roots.size != 32 * max(1, n):
+            raise ValueError(f"{n} proofs but {roots.size} bytes of data roots")
+        if commitments is None:
+            claimed = self.commitments.reshape(-1)
+        else:
+            claimed = np.frombuffer(b"".join(bytes(c) for c in commitments), dtype=np.uint8)
+        if claimed.size != 32 * n:
+            raise ValueError(f"{n} proofs but {claimed.size} bytes of commitments")
+        if not claimed.size:
+            claimed = np.zeros(32, dtype=np.uint8)
+        b = _lib.CommitmentProofBatch()
+        b.n_proofs, b.ns_len, b.threshold = n, 29, self.threshold
+        b.data_roots = roots.ctypes.data_as(_lib.CommitmentProofBatch._u8p)
+        b.commitments = claimed.ctypes.data_as(_lib.CommitmentProofBatch._u8p)
+        for name, t in _lib.CommitmentProofBatch._fields_:
+            if name in self.FIELDS and name != "commitments":
+                setattr(b, name, getattr(self, name).ctypes.data_as(t))
+        b.n_nodes, b.n_roots, b.n_aunts = len(self.nodes), len(self.subtree_roots), len(self.aunts)
+        b._keep = (roots, claimed, self)   # the struct borrows the arrays
+        return b
+
+    def verify(self, data_root, commitments=None, ctx=None) -> np.ndarray:
+        """cda_commitment_proofs_verify of the batch: the verdict per proof
+        (COMMITMENT_VERDICT_TEXT)."""
+        ctx = ctx or default_context()
+        b = self.batch(data_root, commitments)
+        verdict = np.full(max(1, len(self)), 255, dtype=np.uint8)
+        ctx.check(ctx.lib.cda_commitment_proofs_verify(ctx.h, C.byref(b), ptr(verdict)))
+        return verdict[:len(self)]
+
+    def proofs(self) -> list:
+        """One CommitmentProof per blob."""
+        W = 2 * self.k
+        nb, rb, lb, ab, sb = (a.tobytes() for a in (self.nodes, self.row_roots, self.rfc_leaf_hash, self.aunts,
+                                                    self.subtree_roots))
+        seg_off, node_off, aunt_off = self.seg_off.tolist(), self.node_off.tolist(), self.aunt_off.tolist()
+        root_off = self.root_off.tolist()
+        st, en, idx = self.nmt_start.tolist(), self.nmt_end.tolist(), self.rfc_index.tolist()
+        r0, r1 = self.start_row.tolist(), self.end_row.tolist()
+        cut = lambda b, lo, hi, sz: [b[i * sz:(i + 1) * sz] for i in range(lo, hi)]  # noqa: E731
+        out = []
+        for i in range(len(self)):
+            segs = range(seg_off[i], seg_off[i + 1])
+            sp = [NMTProof(st[g], en[g], cut(nb, node_off[g], node_off[g + 1], NMT_ROOT_SIZE)) for g in segs]
+            rp = [Proof(2 * W, idx[g], lb[32 * g:32 * (g + 1)], cut(ab, aunt_off[g], aunt_off[g + 1], 32))
+                  for g in segs]
+            out.append(CommitmentProof(
+                subtree_roots=cut(sb, root_off[segs.start], root_off[segs.stop], NMT_ROOT_SIZE),
+                subtree_root_proofs=sp, namespace=self.namespaces[i].tobytes(),
+                row_proof=RowProof(cut(rb, segs.start, segs.stop, NMT_ROOT_SIZE), rp, r0[i], r1[i])))
+        return out
+
+
+def build_commitment_proof_batch(proofs, data_roots, commitments, subtree_root_threshold: int = 64,
+                                 roots_per_row=None):
+    """The cda_commitment_proof_batch of CommitmentProof objects (any mix of
+    square widths) and the arrays it points into.  A proof's subtree roots are
+    dealt to its rows by the cover's counts for the rows' ranges and the
+    threshold -- the last row takes what remains, so a proof with too many or
+    too few roots fails there; roots_per_row (one list of counts per proof)
+    overrides that split."""
+    from . import inclusion
+    u8p, u32p, i32p, i64p = (C.POINTER(t) for t in (C.c_uint8, C.c_uint32, C.c_int32, C.c_int64))
+    keep = []
+
+    def arr(a, t):
+        keep.append(a)
+        return a.ctypes.data_as(t)
+
+    def offsets(counts):
+        return np.cumsum([0] + list(counts), dtype=np.int64).astype(np.uint32)
+
+    segs, root_counts = [], []
+    for i, p in enumerate(proofs):
+        rows = list(zip(p.subtree_root_proofs, p.row_proof.row_roots, p.row_proof.proofs))
+        if roots_per_row is not None and roots_per_row[i] is not None:
+            counts = list(roots_per_row[i])
+        else:
+            n_sh = sum(max(0, q.end - q.start) for q, _, _ in rows)
+            w = inclusion.sub_tree_width(n_sh, subtree_root_threshold) if n_sh else 1
+            counts, left = [], len(p.subtree_roots)
+            for j, (q, _, _) in enumerate(rows):
+                c = _cover_count(q.start, q.end, w) if j + 1 < len(rows) else left
+                c = min(c, left)
+                counts.append(c)
+                left -= c
+        segs += rows
+        root_counts += counts
+    b = _lib.CommitmentProofBatch()
+    b.n_proofs, b.ns_len, b.threshold = len(proofs), 29, subtree_root_threshold
+    b.data_roots = arr(_bytes_array(data_roots), u8p)
+    b.commitments = arr(_bytes_array(commitments), u8p)
+    b.seg_off = arr(offsets(len(p.subtree_root_proofs) for p in proofs), u32p)
+    b.nmt_start = arr(np.array([q.start for q, _, _ in segs] or [0], dtype=np.int32), i32p)
+    b.nmt_end = arr(np.array([q.end for q, _, _ in segs] or [0], dtype=np.int32), i32p)
+    b.node_off = arr(offsets(len(q.nodes) for q, _, _ in segs), u32p)
+    b.nodes = arr(_bytes_array(x for q, _, _ in segs for x in q.nodes), u8p)
+    b.n_nodes = sum(len(q.nodes) for q, _, _ in segs)
+    b.root_off = arr(offsets(root_counts), u32p)
+    b.subtree_roots = arr(_bytes_array(x for p in proofs for x in p.subtree_roots), u8p)
+    b.n_roots = sum(len(p.subtree_roots) for p in proofs)
+    b.row_roots = arr(_bytes_array(r for _, r, _ in segs), u8p)
+    b.rfc_total = arr(np.array([m.total for _, _, m in segs] or [0], dtype=np.int64), i64p)
+    b.rfc_index = arr(np.array([m.index for _, _, m in segs] or [0], dtype=np.int64), i64p)
+    b.rfc_leaf_hash = arr(_bytes_array(m.leaf_hash for _, _, m in segs), u8p)
+    b.aunt_off = arr(offsets(len(m.aunts) for _, _, m in segs), u32p)
+    b.aunts = arr(_bytes_array(a for _, _, m in segs for a in m.aunts), u8p)
+    b.n_aunts = sum(len(m.aunts) for _, _, m in segs)
+    return b, keep
+
+
+def _cover_count(s0: int, e0: int, w: int) -> int:
+    """The number of subtree roots of the leaf range [s0, e0) with width w
+    (csrc/commitment_proofs_plan.h subtree_cover_count)."""
+    n, c = 0, s0
+    while c < e0:
+        r = w
+        while c % r or c + r > e0:
+            r //= 2
+        n, c = n + 1, c + r
+    return n
+
+
+def _commitment_proof_well_formed(p, data_root, commitment) -> bool:
+    """A proof the batch call can carry: 90-byte nodes and roots, 32-byte
+    hashes, int32 ranges within the library's bound, as many row roots and
+    merkle proofs as NMT proofs."""
+    rp = p.row_proof
+    return len(data_root) == 32 and len(commitment) == 32 and len(p.namespace) == 29 and \
+        len(p.subtree_root_proofs) == len(rp.row_roots) == len(rp.proofs) and \
+        all(len(r) == NMT_ROOT_SIZE for r in p.subtree_roots) and all(len(r) == NMT_ROOT_SIZE for r in rp.row_roots) and \
+        all(len(x) == NMT_ROOT_SIZE for q in p.subtree_root_proofs for x in q.nodes) and \
+        all(0 <= q.start < q.end <= _lib.VERIFY_MAX_LEAVES for q in p.subtree_root_proofs) and \
+        all(_proof_well_formed(m) for m in rp.proofs)
+
+
+def validate_commitment_proofs(proofs, data_roots, commitments, subtree_root_threshold: int = 64, ctx=None) -> list:
+    """CommitmentProof.validate for many proofs, from squares of any width, in
+    one cda_commitment_proofs_verify call: per proof None or the verdict's
+    text.  A proof with a field of the wrong length, or without a row, cannot
+    be one blob's and is answered ERR_NOT_A_BLOB without reaching the GPU."""
+    if not len(proofs) == len(data_roots) == len(commitments):
+        raise ValueError(f"{len(proofs)} proofs, {len(data_roots)} data roots, {len(commitments)} commitments")
+    out = [ERR_NOT_A_BLOB] * len(proofs)
+    idx = [i for i, p in enumerate(proofs) if _commitment_proof_well_formed(p, data_roots[i], commitments[i])]
+    if idx:
+        ctx = ctx or default_context()
+        b, keep = build_commitment_proof_batch([proofs[i] for i in idx], [bytes(data_roots[i]) for i in idx],
+                                               [bytes(commitments[i]) for i in idx], subtree_root_threshold)
+        verdict = np.full(len(idx), 255, dtype=np.uint8)
+        ctx.check(ctx.lib.cda_commitment_proofs_verify(ctx.h, C.byref(b), ptr(verdict)))
+        del keep
+        for i, v in zip(idx, verdict.tolist()):
+            out[i] = COMMITMENT_VERDICT_TEXT[v]
+    return out
 
 
 # ------------------------------------------------------------ verification
@@ -702,3 +985,97 @@ def query_share_inclusion_proof(path, txs, app_version: int = 2, ctx=None) -> Sh
     sq = square.construct(txs, square.SQUARE_SIZE_UPPER_BOUND, square.SUBTREE_ROOT_THRESHOLD, ctx=ctx)
     ns = parse_namespace(sq, begin, end)
     return new_share_inclusion_proof(sq.to_bytes(), ns, begin, end, ctx)
+
+
+def _pb_fields(buf: bytes):
+    """(field number, wire type, value) of a protobuf message; ValueError if it
+    does not parse."""
+    i, n = 0, len(buf)
+
+    def varint():
+        nonlocal i
+        v = shift = 0
+        while True:
+            if i >= n or shift > 63:
+                raise ValueError("malformed varint")
+            c = buf[i]
+            i += 1
+            v |= (c & 0x7F) << shift
+            shift += 7
+            if c < 0x80:
+                return v
+
+    while i < n:
+        key = varint()
+        fn, wt = key >> 3, key & 7
+        if wt == 0:
+            yield fn, wt, varint()
+        elif wt == 2:
+            ln = varint()
+            if i + ln > n:
+                raise ValueError("field beyond the message")
+            yield fn, wt, buf[i:i + ln]
+            i += ln
+        elif wt in (1, 5):
+            ln = 8 if wt == 1 else 4
+            if i + ln > n:
+                raise ValueError("field beyond the message")
+            yield fn, wt, buf[i:i + ln]
+            i += ln
+        else:
+            raise ValueError(f"wire type {wt}")
+
+
+def blob_tx_blobs(tx: bytes):
+    """The blobs of a BlobTx and what its MsgPayForBlobs commits to: a list of
+    (share count, share commitment or None) in the tx's order, or None if tx
+    is not a BlobTx (go-square blob.UnmarshalBlobTx: type_id "BLOB")."""
+    from . import inclusion
+    try:
+        top = list(_pb_fields(tx))
+        if not any(fn == 3 and wt == 2 and v == b"BLOB" for fn, wt, v in top):
+            return None
+        inner = b"".join(v for fn, wt, v in top if fn == 1 and wt == 2)
+        sizes = []
+        for fn, wt, v in top:
+            if fn == 2 and wt == 2:
+                sizes.append(sum(len(d) for f, w, d in _pb_fields(v) if f == 2 and w == 2))
+    except ValueError:
+        return None
+    commits = []
+    try:   # TxRaw.body_bytes -> TxBody.messages -> Any{type_url, value} -> MsgPayForBlobs.share_commitments
+        body = b"".join(v for fn, wt, v in _pb_fields(inner) if fn == 1 and wt == 2)
+        for fn, wt, v in _pb_fields(body):
+            if fn != 1 or wt != 2:
+                continue
+            msg = {f: d for f, w, d in _pb_fields(v) if w == 2}
+            if msg.get(1) == b"/celestia.blob.v1.MsgPayForBlobs":
+                commits = [d for f, w, d in _pb_fields(msg.get(2, b"")) if f == 4 and w == 2]
+                break
+    except ValueError:
+        commits = []
+    return [(inclusion.sparse_shares_needed(sz), commits[i] if i < len(commits) else None)
+            for i, sz in enumerate(sizes)]
+
+
+def new_blob_commitment_proofs(txs, app_version: int = 2, ctx=None) -> list:
+    """The commitment proof of every blob of a block, in PFB order (blob txs in
+    block order, a tx's blobs in its order): a list of (CommitmentProof,
+    claimed share commitment or None when the PFB does not decode).  The blob
+    starts are square.Construct's share indexes, the lengths the blobs', the
+    commitments the PFBs'; one square.Construct, one resident square, one
+    cda_square_commitment_proofs call."""
+    from . import square
+    ub, thr = square.SQUARE_SIZE_UPPER_BOUND, square.SUBTREE_ROOT_THRESHOLD   # appconsts, every version
+    blobs = [b for tx in txs for b in (blob_tx_blobs(tx) or [])]
+    if not blobs:
+        return []
+    _, _, share_indexes = square.layout(txs, ub, thr)
+    if len(share_indexes) != len(blobs):
+        raise _lib.CdaError(_lib.CDA_ERR_INVALID, f"the layout places {len(share_indexes)} blobs, the txs hold {len(blobs)}")
+    sq = ResidentSquare(np.frombuffer(square.construct(txs, ub, thr, ctx=ctx).to_bytes(), dtype=np.uint8), ctx)
+    try:
+        batch = sq.commitment_proofs(share_indexes, [n for n, _ in blobs], thr)
+    finally:
+        sq.close()
+    return list(zip(batch.proofs(), [c for _, c in blobs]))

@@ -10,6 +10,7 @@
 
 #include "../../include/cda.h"
 #include "engine.h"
+#include "commitment_proofs_plan.h"
 #include "share_proofs_plan.h"
 #include "split_layout.h"
 
@@ -634,6 +635,35 @@ int cda_square_share_proofs(cda_square* sq, const uint32_t* starts, const uint32
         if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
         return e.square_share_proofs(&sq->sq, starts, ends, n, *out);
     });
+}
+
+int cda_square_commitment_proofs_plan(uint32_t k, const uint32_t* starts, const uint32_t* share_lens, uint32_t n,
+                                      uint32_t threshold, cda_commitment_proofs_plan_t* out) {
+    // Host-only (no device work), no context.
+    return host_only(nullptr, [&](std::string* err) -> int {
+        if (!out) {
+            *err = "null buffer";
+            return CDA_ERR_INVALID;
+        }
+        cda::CommitmentProofsPlan p;
+        *err = cda::commitment_proofs_plan(k, starts, share_lens, n, threshold, &p);
+        if (!err->empty()) return CDA_ERR_INVALID;
+        *out = cda_commitment_proofs_plan_t{p.n_segments, p.n_roots, p.n_nodes, p.n_aunts, p.aunts_per_segment};
+        return CDA_OK;
+    });
+}
+
+int cda_square_commitment_proofs(cda_square* sq, const uint32_t* starts, const uint32_t* share_lens, uint32_t n,
+                                 uint32_t threshold, const cda_commitment_proofs_out* out) {
+    if (!sq) return CDA_ERR_INVALID;
+    return guarded(sq->ctx, [&](cda::Engine& e) -> int {
+        if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.square_commitment_proofs(&sq->sq, starts, share_lens, n, threshold, *out);
+    });
+}
+
+int cda_commitment_proofs_verify(cda_ctx* ctx, const cda_commitment_proof_batch* b, uint8_t* verdict) {
+    return guarded(ctx, [&](cda::Engine& e) -> int { return e.commitment_proofs_verify(b, verdict); });
 }
 
 int cda_square_namespace_plan(cda_square* sq, const uint8_t* namespaces, uint32_t n, cda_namespace_plan_t* out) {

@@ -596,8 +596,15 @@ hipError_t launch_slot_merkle_roots(const uint8_t* slots, const uint32_t* bt, ui
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
+    return launch_digest_merkle_roots(dig, bt, n_sets, max_n, out, s);
+}
+
+hipError_t launch_digest_merkle_roots(const uint32_t* dig, const uint32_t* bt, uint32_t n_sets, uint32_t max_n,
+                                      uint8_t* out, hipStream_t s) {
+    if (n_sets == 0) return hipSuccess;
     const uint32_t mt = max_n ? max_n : 1;
     const size_t lds = (size_t)(mt + (mt + 1) / 2) * 32;
+    static_assert((size_t)(kMerkleRootsMaxItems + (kMerkleRootsMaxItems + 1) / 2) * 32 <= 64 * 1024);
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     hipLaunchKernelGGL(commitment_kernel, dim3(n_sets), dim3(64), lds, s, dig, bt, mt, out);
     return hipGetLastError();

@@ -19,6 +19,8 @@ struct cda_share_proof_batch;   // include/cda.h
 struct cda_share_proofs_out;
 struct cda_namespace_plan_t;
 struct cda_namespace_proofs_out;
+struct cda_commitment_proofs_out;
+struct cda_commitment_proof_batch;
 struct cda_namespace_proof_batch;
 struct cda_befp_batch;
 namespace cda {
@@ -109,6 +111,12 @@ struct DevBuf {
 // entries, at most max_n per set); dig = scratch, 8 words per slot.
 hipError_t launch_slot_merkle_roots(const uint8_t* slots, const uint32_t* bt, uint32_t n_sets, uint32_t n_slots,
                                     uint32_t max_n, uint32_t* dig, uint8_t* out, hipStream_t s);
+// The second half of it alone, for callers whose kernel wrote the leaf digests (8 state words per item): the
+// root of each set of digests [bt[b], bt[b+1]), one launch.  hipErrorInvalidValue if max_n exceeds
+// kMerkleRootsMaxItems (the levels of a set live in one workgroup's LDS).
+constexpr uint32_t kMerkleRootsMaxItems = 1365;
+hipError_t launch_digest_merkle_roots(const uint32_t* dig, const uint32_t* bt, uint32_t n_sets, uint32_t max_n,
+                                      uint8_t* out, hipStream_t s);
 
 // A square kept in HBM after extension (proof.hip): the EDS, every level of
 // every row tree (level 0 = the W x W leaf slots, level L = [W][W >> L] 96-B
@@ -307,6 +315,13 @@ class Engine {
     // What both producers of a segment table end in (share_proofs.hip): the table up, the proof kernel's one
     // launch, the requested outputs back; complete on return.
     int emit_segments(ResidentSquare* sq, const SegmentEmit& em);
+    // Blob commitment proofs of n blobs (start, share_len) in one launch of the same kernel (share_proofs.hip):
+    // per row the subtree roots of commitment_proofs_plan.h's cover, the nodes and the row proof of the share
+    // proofs; out.commitments costs one further launch (commit.hip).  A square whose push order failed answers
+    // CDA_ERR_PUSH_ORDER.
+    int square_commitment_proofs(ResidentSquare* sq, const uint32_t* starts, const uint32_t* share_lens, uint32_t n,
+                                 uint32_t threshold, const cda_commitment_proofs_out& out);
+    int fail_unordered_square(const ResidentSquare* sq, const char* why);   // CDA_ERR_PUSH_ORDER, po_* set
     // All shares of n namespaces with nmt ProveNamespace's proofs, absence proofs included (namespace_proofs.hip):
     // one search launch whose (query, row) words come back, the host plan (namespace_proofs_plan.h), and for the
     // proofs emit_segments.  A square whose push order failed answers CDA_ERR_PUSH_ORDER.
@@ -346,6 +361,10 @@ class Engine {
     // selection (verify.hip): verdict[q] = 0 valid, 1 rows, 2 hash or absence leaf, 3 incomplete.
     int namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const cda_namespace_proof_batch* b,
                                 uint8_t* verdict);
+    // Blob commitment proofs (commitment_verify.hip): verdict[p] = 0 valid, 4 not one contiguous blob, 1 row
+    // proof, 2 subtree roots and nodes do not rebuild the row root, 3 commitment.  Four launches, one
+    // synchronisation.
+    int commitment_proofs_verify(const cda_commitment_proof_batch* b, uint8_t* verdict);
 
     // Bad-encoding fraud proofs (befp.hip).  befp_build: every cell of vector (axis, index) of a host (eds) or
     // device (d_eds) square whose orthogonal vector hashes to its DAH root, with its proof against that root;
@@ -356,7 +375,8 @@ class Engine {
     int befp_verify(const cda_befp_batch* b, uint8_t* verdict, uint8_t* rebuilt_roots);
 
     // Stage timing with HIP events on the launch stream (bench / profiling).
-    enum Stage { kStageRsQ0 = 0, kStageRsQ3, kStageOrder, kStageLeaves, kStageLevels, kStageDataRoot, kNumStages };
+    enum Stage { kStageRsQ0 = 0, kStageRsQ3, kStageOrder, kStageLeaves, kStageLevels, kStageDataRoot,
+                 kStageCommitmentProofs, kStageCommitmentVerify, kNumStages };
     void set_profiling(bool on) { profiling_ = on; }
     int collect_stage_times(double* ms, uint32_t* counts, int n);
 

@@ -116,20 +116,24 @@ __global__ __launch_bounds__(64 * kSearchWaves) void namespace_search_kernel(con
 
 }  // namespace
 
+// What the calls that need nmt's own trees answer for a square whose push order failed.
+int Engine::fail_unordered_square(const ResidentSquare* sq, const char* why) {
+    const push_order::Violation v = push_order::decode(sq->push_err);
+    po_axis = v.axis;
+    po_index = v.index;
+    po_pos = v.pos;
+    return fail(CDA_ERR_PUSH_ORDER, std::string("the square's ") + (v.axis == 0 ? "row " : "column ") +
+                                        std::to_string(v.index) + " is not ordered by namespace at position " +
+                                        std::to_string(v.pos) + ": " + why);
+}
+
 int Engine::square_namespace_search(ResidentSquare* sq, const uint8_t* namespaces, uint32_t n,
                                     std::vector<uint32_t>* words) {
     const uint32_t k = sq->k;
     const std::string bad = namespace_queries_check(k, namespaces, n);
     if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
-    if (sq->push_err != push_order::kOrdered) {
-        const push_order::Violation v = push_order::decode(sq->push_err);
-        po_axis = v.axis;
-        po_index = v.index;
-        po_pos = v.pos;
-        return fail(CDA_ERR_PUSH_ORDER, std::string("the square's ") + (v.axis == 0 ? "row " : "column ") +
-                                            std::to_string(v.index) + " is not ordered by namespace at position " +
-                                            std::to_string(v.pos) + ": nmt builds no tree of it, so no namespace proof");
-    }
+    if (sq->push_err != push_order::kOrdered)
+        return fail_unordered_square(sq, "nmt builds no tree of it, so no namespace proof");
     words->assign((size_t)n * k, 0);
     if (n == 0) return CDA_OK;
     const uint32_t row_blocks = (k + 63) / 64;

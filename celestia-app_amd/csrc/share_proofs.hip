@@ -36,11 +36,23 @@
 // namespace proofs end in too (namespace_proofs.hip).  Their absence segments
 // (kSegAbsence) have no share units, and their leaf is one more staged slot
 // behind the row root, written packed to absence_leaf.
+//
+// Blob commitment proofs (cda_square_commitment_proofs) are a third producer,
+// here: segments of kind kSegSubtree have no shares, and beside the nodes and
+// the row proof their wave gathers the subtree roots of the segment's range --
+// node `index` of row level `level` for every item of the cover of
+// commitment_proofs_plan.h -- through the same stage row in tiles of
+// kProofSlots slots, written packed to subtree_roots; with root_dig each root
+// also leaves as its RFC-6962 leaf digest for the commitments' one launch
+// (commit.hip).  That half is the SUB instantiation of the kernel, so the
+// share and namespace proofs run the code they ran without it.
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/cda.h"
+#include "commitment_proofs_plan.h"
 #include "engine.h"
 #include "out_regions.h"
 #include "resident_proof_dev.h"
@@ -71,6 +83,8 @@ struct ShareProofsArgs {
     uint8_t* namespaces;
     uint32_t* flags;            // one_namespace bytes, preset to 1
     uint8_t* absence_leaf;      // the namespace proofs' output (namespaces and flags are then NULL)
+    uint8_t* subtree_roots;     // the commitment proofs' outputs (SUB)
+    uint32_t* root_dig;         // 8 state words per subtree root: sha256(0x00 || root)
 };
 
 __device__ __forceinline__ SegEntry load_seg(const SegEntry* p) {
@@ -78,8 +92,10 @@ __device__ __forceinline__ SegEntry load_seg(const SegEntry* p) {
     return SegEntry{lo.x, lo.y, lo.z, lo.w, (uint64_t)hi.x | ((uint64_t)hi.y << 32), hi.z, hi.w};
 }
 
-// One wavefront per segment; every wave of the workgroup reaches the barrier.
-__device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*stage)[stage_row(kProofSlots)]) {
+// One wavefront per segment; every wave of the workgroup reaches every barrier.
+template <bool SUB>
+__device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*stage)[stage_row(kProofSlots)],
+                                           uint32_t* tiles) {
     const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const uint32_t g = blockIdx.x * kProofWaves + wave;
     const bool live = g < a.n_segs;   // uniform over the wave
@@ -109,12 +125,49 @@ __device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*sta
         store_root_proof(v.rfc, W, A, row, g, a.leaf_hash, a.aunts, lane);   // Index = row among the 4k roots
     }
     __syncthreads();
-    if (!live) return;
     const uint8_t* sb = reinterpret_cast<const uint8_t*>(st);
-    if (a.nodes) store_packed<kNode>(sb, cnt, a.nodes + (uint64_t)e.node_off * kNode, lane);
-    if (a.row_roots) store_packed<kNode>(sb + cnt * kSlot, 1, a.row_roots + (uint64_t)g * kNode, lane);
-    if (a.namespaces && first) store_packed<kNs>(sb + (cnt + 1) * kSlot, 1, a.namespaces + (uint64_t)e.proof * kNs, lane);
-    if (a.absence_leaf) store_packed<kNode>(sb + (cnt + 1) * kSlot, 1, a.absence_leaf + (uint64_t)g * kNode, lane);
+    if (live) {
+        if (a.nodes) store_packed<kNode>(sb, cnt, a.nodes + (uint64_t)e.node_off * kNode, lane);
+        if (a.row_roots) store_packed<kNode>(sb + cnt * kSlot, 1, a.row_roots + (uint64_t)g * kNode, lane);
+        if (a.namespaces && first)
+            store_packed<kNs>(sb + (cnt + 1) * kSlot, 1, a.namespaces + (uint64_t)e.proof * kNs, lane);
+        if (a.absence_leaf) store_packed<kNode>(sb + (cnt + 1) * kSlot, 1, a.absence_leaf + (uint64_t)g * kNode, lane);
+    }
+    if constexpr (SUB) {
+        // The subtree roots of [s0, e0), kProofSlots at a time through the stage row.  The workgroup's waves
+        // run the most tiles any of them needs, so that the barriers are uniform over the workgroup.
+        const bool sub = live && (e.range & kSegSubtree) != 0;
+        const uint32_t log_w = e.unit_off;
+        const uint32_t n_roots = sub ? subtree_cover_walk(s0, e0, log_w, 0xFFFFFFFFu).index : 0u;
+        if (lane == 0) tiles[wave] = (n_roots + kProofSlots - 1) / kProofSlots;
+        __syncthreads();   // also: the stores above have read the stage row
+        uint32_t n_tiles = 0;
+        for (uint32_t w = 0; w < kProofWaves; w++) n_tiles = max(n_tiles, tiles[w]);
+        for (uint32_t t = 0; t < n_tiles; t++) {
+            const uint32_t at = t * kProofSlots;
+            const uint32_t here = at < n_roots ? min(kProofSlots, n_roots - at) : 0u;   // uniform over the wave
+            if (here)
+                stage_slots(st, here, lane, [&](uint32_t j) {
+                    const TreeNode nd = subtree_cover_walk(s0, e0, log_w, at + j);
+                    return StagedSlot{v.levels + level_offset(W, nd.level, 0, kSlot) +
+                                          ((uint64_t)row * (W >> nd.level) + nd.index) * kSlot, j};
+                });
+            __syncthreads();
+            if (here) {
+                const uint64_t first_root = e.share_off + at;
+                if (a.subtree_roots) store_packed<kNode>(sb, here, a.subtree_roots + first_root * kNode, lane);
+                if (a.root_dig && lane < here) {
+                    uint32_t I[kSlotWords], d[8];
+                    load_slot_be(sb + lane * kSlot, I);
+                    rfc_leaf_u<false>(I, d, false);
+                    uint4* o = reinterpret_cast<uint4*>(a.root_dig + (first_root + lane) * 8);
+                    o[0] = make_uint4(d[0], d[1], d[2], d[3]);
+                    o[1] = make_uint4(d[4], d[5], d[6], d[7]);
+                }
+            }
+            __syncthreads();   // the row is read before the next tile overwrites it
+        }
+    }
 }
 
 // One wavefront per unit of at most kUnitShares shares of one segment.
@@ -166,9 +219,11 @@ __device__ __forceinline__ void share_part(const ShareProofsArgs& a) {
         atomicAnd(a.flags + e.proof / 4, ~(0xFFu << (8 * (e.proof % 4))));
 }
 
+template <bool SUB>
 __global__ __launch_bounds__(64 * kProofWaves) void share_proofs_kernel(const ShareProofsArgs a) {
     __shared__ uint4 stage[kProofWaves][stage_row(kProofSlots)];
-    if (blockIdx.x < a.proof_blocks) proof_part(a, stage);   // uniform over the workgroup
+    __shared__ uint32_t tiles[kProofWaves];
+    if (blockIdx.x < a.proof_blocks) proof_part<SUB>(a, stage, tiles);   // uniform over the workgroup
     else share_part(a);
 }
 
@@ -246,6 +301,74 @@ int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, cons
     return emit_segments(sq, em);
 }
 
+// cda_square_commitment_proofs: a blob is the share range [start, start + share_len) after NextShareIndex, and
+// its segments are the share proof's of that range with the subtree roots in the place of the shares.
+int Engine::square_commitment_proofs(ResidentSquare* sq, const uint32_t* starts, const uint32_t* share_lens,
+                                     uint32_t n, uint32_t threshold, const cda_commitment_proofs_out& o) {
+    const uint32_t k = sq->k, W = 2 * k, D = sq->log_w, A = D + 1;
+    CommitmentProofsPlan plan;
+    const std::string bad = commitment_proofs_plan(k, starts, share_lens, n, threshold, &plan);
+    if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
+    if (sq->push_err != push_order::kOrdered)
+        return fail_unordered_square(sq, "nmt builds no tree of it, so no commitment proof");
+    if (o.seg_off) o.seg_off[0] = 0;
+    if (o.node_off) o.node_off[0] = 0;
+    if (o.root_off) o.root_off[0] = 0;
+    if (o.aunt_off) o.aunt_off[0] = 0;
+    if (n == 0) return CDA_OK;
+    const uint32_t S = plan.n_segments;
+    // the table, the (unused) one_namespace bytes, the first root of every proof for the commitments
+    const size_t flag_words = ((size_t)n + 3) / 4;
+    SegmentEmit em;
+    em.up.resize((size_t)S * kSegWords + flag_words + n + 1);
+    SegEntry* segs = em.segs();
+    uint32_t* first_root = em.up.data() + (size_t)S * kSegWords + flag_words;
+    uint32_t g = 0, node_at = 0, root_at = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        NormalisedBlob b{};
+        (void)normalise_blob(k, i, starts[i], share_lens[i], threshold, &b);   // checked by the plan
+        const uint32_t first_cell = (b.start / k) * W + b.start % k, log_w = ceil_log2(b.w);
+        first_root[i] = root_at;
+        for_each_segment(k, i, b.start, b.end, [&](const ShareProofSegment& sg) {
+            const uint32_t count = range_proof_count(D, sg.s0, sg.e0);
+            segs[g] = SegEntry{sg.row, sg.s0 | (sg.e0 << 16) | kSegSubtree, node_at, log_w, root_at, i, first_cell};
+            if (o.nmt_start) o.nmt_start[g] = (int32_t)sg.s0;
+            if (o.nmt_end) o.nmt_end[g] = (int32_t)sg.e0;
+            if (o.rfc_total) o.rfc_total[g] = 2ll * W;
+            if (o.rfc_index) o.rfc_index[g] = sg.row;
+            node_at += count;
+            root_at += subtree_cover_count(sg.s0, sg.e0, b.w);
+            g++;
+            if (o.node_off) o.node_off[g] = node_at;
+            if (o.root_off) o.root_off[g] = root_at;
+            if (o.aunt_off) o.aunt_off[g] = g * A;
+        });
+        em.max_roots = std::max(em.max_roots, root_at - first_root[i]);
+        if (o.seg_off) o.seg_off[i + 1] = g;
+        if (o.start_row) o.start_row[i] = b.start / k;
+        if (o.end_row) o.end_row[i] = (b.end - 1) / k;
+        if (o.norm_start) o.norm_start[i] = b.start;
+    }
+    first_root[n] = root_at;
+    if (o.commitments && em.max_roots > kMerkleRootsMaxItems)
+        return fail(CDA_ERR_INVALID, "a blob has " + std::to_string(em.max_roots) + " subtree roots; commitments takes at most " +
+                                         std::to_string(kMerkleRootsMaxItems) + " per blob");
+    em.n_segs = S;
+    em.n_flags = n;
+    em.node_slots = plan.n_nodes;
+    em.n_aunts = plan.n_aunts;
+    em.n_roots = plan.n_roots;
+    em.nodes = o.nodes;
+    em.row_roots = o.row_roots;
+    em.leaf_hash = o.rfc_leaf_hash;
+    em.aunts = o.aunts;
+    em.namespaces = o.namespaces;
+    em.subtree_roots = o.subtree_roots;
+    em.commitments = o.commitments;
+    em.stage = kStageCommitmentProofs;
+    return emit_segments(sq, em);
+}
+
 // The table-to-launch half of both producers (share ranges above, namespaces in namespace_proofs.hip): one
 // upload, one launch whatever the table holds, the requested outputs back.
 int Engine::emit_segments(ResidentSquare* sq, const SegmentEmit& em) {
@@ -257,21 +380,38 @@ int Engine::emit_segments(ResidentSquare* sq, const SegmentEmit& em) {
                r_sh = out.add(em.shares, (size_t)em.n_shares * kShare),
                r_ns = out.add(em.namespaces, (size_t)em.n_flags * kNs),
                r_al = out.add(em.absence_leaf, (size_t)S * kNode),
-               r_fl = out.add_at(em.one_namespace, (size_t)S * sizeof(SegEntry), em.n_flags);
+               r_fl = out.add_at(em.one_namespace, (size_t)S * sizeof(SegEntry), em.n_flags),
+               r_sr = out.add(em.subtree_roots, em.n_roots * kNode),
+               r_cm = out.add(em.commitments, (size_t)em.n_flags * 32);
+    // scratch behind the outputs: the subtree roots' leaf digests
+    const size_t dig_off = out.total(), dig_bytes = em.commitments ? em.n_roots * 32 : 0;
     hipStream_t s = stream_;
-    CDA_TRY(ensure(sq->scratch, out.total(), "hipMalloc"));
+    CDA_TRY(ensure(sq->scratch, out.total() + dig_bytes, "hipMalloc"));
     uint8_t* scr = sq->scratch.as<uint8_t>();
     CDA_TRY(h2d(scr, em.up.data(), em.up.size() * 4, s, "H2D share proofs"));
     ShareProofsArgs a{sq->view(), reinterpret_cast<const SegEntry*>(scr), S, 0, 0, r_nd.dev(scr), r_rt.dev(scr),
                       r_lh.dev(scr), r_au.dev(scr), r_sh.dev(scr), r_ns.dev(scr),
-                      reinterpret_cast<uint32_t*>(r_fl.dev(scr)), r_al.dev(scr)};
-    const bool proof_half = a.nodes || a.row_roots || a.leaf_hash || a.aunts || a.namespaces || a.absence_leaf;
+                      reinterpret_cast<uint32_t*>(r_fl.dev(scr)), r_al.dev(scr), r_sr.dev(scr),
+                      em.commitments ? reinterpret_cast<uint32_t*>(scr + dig_off) : nullptr};
+    const bool sub = a.subtree_roots || a.root_dig;
+    const bool proof_half = a.nodes || a.row_roots || a.leaf_hash || a.aunts || a.namespaces || a.absence_leaf || sub;
     a.proof_blocks = proof_half ? (S + kProofWaves - 1) / kProofWaves : 0;
     a.n_units = a.shares || a.flags ? em.n_units : 0;
     const uint32_t blocks = a.proof_blocks + (a.n_units + kProofWaves - 1) / kProofWaves;
     if (blocks) {
-        hipLaunchKernelGGL(share_proofs_kernel, dim3(blocks), dim3(64 * kProofWaves), 0, s, a);
+        if (em.stage >= 0) mark_begin(em.stage, s);
+        if (sub) hipLaunchKernelGGL(share_proofs_kernel<true>, dim3(blocks), dim3(64 * kProofWaves), 0, s, a);
+        else hipLaunchKernelGGL(share_proofs_kernel<false>, dim3(blocks), dim3(64 * kProofWaves), 0, s, a);
+        if (em.stage >= 0) mark_end(s);
         CDA_TRY(launched("share proofs"));
+    }
+    if (em.commitments) {
+        // the first roots of the proofs lie behind the table and the flag words of the upload
+        const uint32_t* bt = reinterpret_cast<const uint32_t*>(scr) + (size_t)S * kSegWords + ((size_t)em.n_flags + 3) / 4;
+        if (em.stage >= 0) mark_begin(em.stage, s);
+        const hipError_t err = launch_digest_merkle_roots(a.root_dig, bt, em.n_flags, em.max_roots, r_cm.dev(scr), s);
+        if (em.stage >= 0) mark_end(s);
+        CDA_TRY(check(err, "commitments of the subtree roots"));
     }
     // the table is pageable and the outputs are the caller's: complete before returning
     return regions_out(out, scr, out.span().bytes <= em.one_copy_max, s, "D2H share proofs");

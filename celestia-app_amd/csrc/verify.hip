@@ -1,4 +1,4 @@
-// verify.hip -- batched verification of share and row proofs.
+// verify.hip -- batched verification of share, row, namespace and blob commitment proofs.
 //
 // Reference behaviour (paths under the celestia-app v3 tree; EXT = module
 // pinned in go.mod):
@@ -35,16 +35,22 @@
 // same batch struct -- an absence segment's one leaf comes from the prover's
 // absence_leaf instead of a hashed share -- then vn_complete_kernel (one lane
 // per proof node: the completeness comparison) and vn_verdict_kernel.
+// Blob commitment proofs (Engine::commitment_proofs_verify) run 3 as it is and
+// kernels of their own for the rest; they are described where they stand,
+// behind the namespace proofs.
 // Every index a kernel uses was validated on the host (Engine::
 // share_proofs_verify, namespace_proofs_verify); the counts that are verdicts (aunts, nodes) are
 // compared before anything is read through them.
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/cda.h"
+#include "commitment_proofs_plan.h"
 #include "engine.h"
 #include "leaf_dev.h"
+#include "resident_proof_dev.h"
 #include "sha_bytes_dev.h"
 
 namespace cda {
@@ -665,6 +671,405 @@ int Engine::namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const 
     CDA_TRY(launched("namespace proof verdicts"));
     std::vector<uint8_t> out(P);
     CDA_TRY(d2h(out.data(), v.verdict, P, s, "D2H verdicts"));
+    CDA_TRY(sync(s));
+    memcpy(verdict, out.data(), P);
+    return CDA_OK;
+}
+
+namespace {
+// ---------------------------------------------------------------------------
+// Blob commitment proofs (cda_commitment_proofs_verify): per row nmt v0.22.0
+// Proof.VerifySubtreeRootInclusion restated -- the subtree roots of the row's
+// range (the cover of commitment_proofs_plan.h) and the nodes of ProveRange
+// rebuild the row root -- and per proof the RFC-6962 root of its subtree roots
+// against the claimed commitment.  Four launches per batch:
+//   1. vp_row_kernel      as for the share proofs;
+//   2. vc_fold_kernel     one wave per segment, below; it also leaves every
+//                         subtree root's RFC-6962 leaf digest (rfc_leaf_u);
+//   3. commit.hip's commitment_kernel over those digests, one wave per proof
+//                         (launch_digest_merkle_roots): the RFC split for any
+//                         count, odd node promoted;
+//   4. vc_verdict_kernel  one lane per proof.
+// "Not one contiguous blob" (4) needs no hashing and is decided on the host;
+// the segments of such a proof are not folded.
+//
+// The fold.  The host has checked s0 % w == 0 and e0 <= k, so the cover is
+// n_w = (e0 - s0) / w nodes of level L = log2 w, then one node per set bit of
+// rem = (e0 - s0) % w, highest first.  Below L at most one node is carried:
+// with bit l of rem set the root of height l is the left sibling of the carry
+// (or, without a carry, takes the right proof node); with it clear the carry
+// takes the right proof node.  That chain (at most 10 hashes) runs on every
+// lane alike.  From level L the run and the carry are the contiguous range
+// [s0 >> L, ..) of level L, folded as vp_fold_kernel folds its leaves: pairs
+// across lanes, per level at most one left and one right proof node, the left
+// ones taken in reverse.  A run of more than kFoldTile nodes (up to 1024 + the
+// carry at k = 1024, w = 1) is folded in tiles aligned to kFoldTile: a tile
+// folds log2 kFoldTile levels to one node -- only the first tile can need left
+// nodes and only the last right ones, in the order of the levels -- and the
+// tiles' nodes (at most 18) are the run of the final fold.
+constexpr uint32_t kFoldTile = CDA_COMMITMENT_FOLD_TILE, kFoldTileLog = 6;
+static_assert(kFoldTile == 1u << kFoldTileLog && kFoldTile == 64, "one lane per node of a tile");
+constexpr uint32_t kFoldMaxD = 11;                       // log2(2 * 1024)
+constexpr uint32_t kFoldNodes = 2 * kFoldMaxD;           // proof nodes of one segment
+constexpr uint32_t kFoldLow = kFoldMaxD - 1;             // roots below level log2 w
+constexpr uint32_t kFoldHalf = kFoldTile / 2 + 1;        // parents of a tile with an odd first index
+constexpr uint32_t kFoldNext = (1024 + 1) / kFoldTile + 2;   // tiles a run of 1025 nodes can span
+constexpr uint8_t kShapeNotABlob = 0xFF;
+
+struct CommitVerify {
+    uint32_t n_proofs, n_segs;
+    const uint32_t* seg_off;
+    const int32_t* nmt_start;
+    const int32_t* nmt_end;
+    const uint32_t* node_off;
+    const uint8_t* nodes;
+    const uint32_t* root_off;
+    const uint8_t* roots;
+    const uint8_t* row_roots;
+    const uint8_t* shape;         // per segment: log2 w | log2(2k) << 4, or kShapeNotABlob
+    const uint8_t* pre;           // per proof: 4 or 0, decided on the host
+    const uint8_t* commitments;   // claimed
+    const uint8_t* got;           // the roots of the subtree roots
+    uint32_t* dig;                // 8 state words per subtree root
+    const uint8_t* row_ok;
+    uint8_t* nmt_ok;
+    uint8_t* verdict;
+};
+
+// `count` packed 90-byte nodes at any address into 96-byte LDS slots (the padding zero), a word per lane.
+__device__ __forceinline__ void stage_packed(uint8_t* slots, const uint8_t* src, uint32_t count, uint32_t tid) {
+    for (uint32_t q = tid; q < count * (uint32_t)kSlotWords; q += 64) {
+        const uint32_t node = q / kSlotWords, at = 4 * (q % kSlotWords);
+        const uint8_t* p = src + (size_t)node * kNode;
+        uint32_t v = 0;
+#pragma unroll
+        for (uint32_t t = 0; t < 4; t++)
+            if (at + t < (uint32_t)kNode) v |= (uint32_t)p[at + t] << (8 * t);
+        reinterpret_cast<uint32_t*>(slots)[q] = v;
+    }
+}
+
+// `levels` levels of the range [a, b) of one tree level, whose nodes lie in src[0 ..): vp_fold_kernel's step.
+// li: left proof nodes still to take (node li - 1 is next); ri: the next right one.  Returns the buffer that
+// holds the result in slot 0.  Uniform over the wave; ends behind a barrier.
+__device__ __forceinline__ uint8_t* fold_levels(uint8_t* src, uint8_t* dst, const uint8_t* nd, uint32_t m, uint32_t a,
+                                                uint32_t b, uint32_t levels, uint32_t& li, uint32_t& ri, bool& bad,
+                                                uint32_t tid) {
+    for (uint32_t q = 0; q < levels; q++) {
+        const bool need_l = a & 1, need_r = b & 1;
+        // the counts were compared with the range's on entry; a node that is not there fails the segment
+        if ((need_l && li == 0) || (need_r && ri >= m)) bad = true;
+        const uint32_t lx = li ? li - 1 : 0, rx = ri < m ? ri : 0;   // inside the staged nodes whatever happens
+        const uint32_t na = a >> 1, nb = (b + 1) >> 1, cnt = nb - na;
+        if (tid < cnt) {
+            const uint32_t p0 = 2 * (na + tid), p1 = p0 + 1;
+            const uint8_t* l = p0 < a ? nd + (size_t)lx * kSlot : src + (size_t)(p0 - a) * kSlot;
+            const uint8_t* r = p1 >= b ? nd + (size_t)rx * kSlot : src + (size_t)(p1 - a) * kSlot;
+            vp_hash_node<true>(kNs, l, r, dst + (size_t)tid * kSlot);
+        }
+        if (need_l && li) li--;
+        if (need_r) ri++;
+        a = na;
+        b = nb;
+        uint8_t* t = src;
+        src = dst;
+        dst = t;
+        __syncthreads();
+    }
+    return src;
+}
+
+// One segment per workgroup of one wave.
+__global__ __launch_bounds__(64) void vc_fold_kernel(const CommitVerify b) {
+    __shared__ __attribute__((aligned(16))) uint8_t nd[kFoldNodes * kSlot];
+    __shared__ __attribute__((aligned(16))) uint8_t low[kFoldLow * kSlot];
+    __shared__ __attribute__((aligned(16))) uint8_t buf_a[kFoldTile * kSlot];
+    __shared__ __attribute__((aligned(16))) uint8_t buf_b[kFoldHalf * kSlot];
+    __shared__ __attribute__((aligned(16))) uint8_t next[kFoldNext * kSlot];
+    const uint32_t s = blockIdx.x, tid = threadIdx.x;
+    const uint8_t shape = b.shape[s];
+    if (shape == kShapeNotABlob) {   // uniform over the workgroup, as every branch below
+        if (tid == 0) b.nmt_ok[s] = 0;
+        return;
+    }
+    const uint32_t L = shape & 15u, D = shape >> 4;
+    const uint32_t s0 = (uint32_t)b.nmt_start[s], e0 = (uint32_t)b.nmt_end[s];   // s0 % 2^L == 0, e0 <= 2^(D - 1)
+    const uint32_t r0 = b.root_off[s], nr = b.root_off[s + 1] - r0;
+    const uint32_t n0 = b.node_off[s], m = b.node_off[s + 1] - n0;
+    const uint32_t n_w = (e0 - s0) >> L, rem = (e0 - s0) & ((1u << L) - 1u);
+    const uint32_t n_low = (uint32_t)__popc(rem);
+    // a root count that is not the cover's, or a node count that is not the range's
+    if (nr != n_w + n_low || m != range_proof_count(D, s0, e0)) {
+        if (tid == 0) b.nmt_ok[s] = 0;
+        return;
+    }
+    const uint8_t* roots = b.roots + (size_t)r0 * kNode;
+    // the commitment's leaves, a root per lane
+    for (uint32_t i = tid; i < nr; i += 64) {
+        uint32_t I[kSlotWords], d[8];
+        load_packed_be(roots + (size_t)i * kNode, I);
+        rfc_leaf_u<false>(I, d, false);
+        uint32_t* o = b.dig + (size_t)(r0 + i) * 8;
+#pragma unroll
+        for (int j = 0; j < 8; j++) o[j] = d[j];
+    }
+    stage_packed(nd, b.nodes + (size_t)n0 * kNode, m, tid);
+    stage_packed(low, roots + (size_t)n_w * kNode, n_low, tid);
+    __syncthreads();
+    uint32_t li = (uint32_t)__popc(s0), ri = li;
+    bool bad = false;
+    // below level L: the chain, the same on every lane
+    uint32_t C[kSlotWords];   // the carry as store_slot takes it
+    bool have = false;
+    uint32_t lx = n_low;      // roots below L still to take: low[lx - 1] is next (the lowest is last)
+    for (uint32_t l = 0; l < L; l++) {
+        const bool bit = (rem >> l) & 1u;
+        if (!bit && !have) continue;
+        uint32_t Lw[kSlotWords], Rw[kSlotWords];
+        if (bit) {
+            load_slot_be(low + (size_t)(--lx) * kSlot, Lw);
+        } else {
+#pragma unroll
+            for (int j = 0; j < kSlotWords; j++) Lw[j] = bswap32(C[j]);
+        }
+        if (bit && have) {
+#pragma unroll
+            for (int j = 0; j < kSlotWords; j++) Rw[j] = bswap32(C[j]);
+        } else {
+            if (ri >= m) bad = true;
+            load_slot_be(nd + (size_t)(ri < m ? ri : 0) * kSlot, Rw);
+            ri++;
+        }
+        hash_node_u<false>(Lw, Rw, C, false);
+        have = true;
+    }
+    // level L: the run and the carry are [lo, hi)
+    uint32_t lo = s0 >> L, hi = lo + n_w + (have ? 1u : 0u), level = L;
+    const uint8_t* run = nullptr;   // the staged run of the final fold; NULL: the roots and the carry
+    if (hi - lo > kFoldTile) {
+        const uint32_t t0 = lo >> kFoldTileLog, t1 = (hi - 1) >> kFoldTileLog;   // t1 - t0 < kFoldNext
+        for (uint32_t t = t0; t <= t1; t++) {
+            const uint32_t a = max(lo, t << kFoldTileLog), e = min(hi, (t + 1) << kFoldTileLog);
+            const uint32_t from_roots = min(e, lo + n_w) - a;   // the carry, if any, is the last node of the run
+            stage_packed(buf_a, roots + (size_t)(a - lo) * kNode, from_roots, tid);
+            if (from_roots < e - a && tid == 0) store_slot(buf_a + (size_t)from_roots * kSlot, C);
+            __syncthreads();
+            const uint8_t* top = fold_levels(buf_a, buf_b, nd, m, a, e, kFoldTileLog, li, ri, bad, tid);
+            if (tid < kSlotPieces)
+                reinterpret_cast<uint4*>(next + (size_t)(t - t0) * kSlot)[tid] = reinterpret_cast<const uint4*>(top)[tid];
+            __syncthreads();
+        }
+        lo = t0;
+        hi = t1 + 1;
+        level += kFoldTileLog;
+        run = next;
+    }
+    const uint32_t cnt = hi - lo;   // <= kFoldTile
+    if (run) {
+        for (uint32_t q = tid; q < cnt * kSlotPieces; q += 64)
+            reinterpret_cast<uint4*>(buf_a)[q] = reinterpret_cast<const uint4*>(run)[q];
+    } else {
+        stage_packed(buf_a, roots, n_w, tid);
+        if (have && tid == 0) store_slot(buf_a + (size_t)n_w * kSlot, C);
+    }
+    __syncthreads();
+    const uint8_t* top = fold_levels(buf_a, buf_b, nd, m, lo, hi, D - level, li, ri, bad, tid);
+    // every node taken, all 90 bytes equal
+    bad = bad || li != 0 || ri != m;
+    const uint8_t* want = b.row_roots + (size_t)s * kNode;
+    for (uint32_t j = tid; j < (uint32_t)kNode; j += 64) bad = bad || top[j] != want[j];
+    const bool any_bad = __syncthreads_or(bad);
+    if (tid == 0) b.nmt_ok[s] = any_bad ? 0 : 1;
+}
+
+__global__ __launch_bounds__(256) void vc_verdict_kernel(const CommitVerify b) {
+    const uint32_t p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= b.n_proofs) return;
+    uint32_t v = b.pre[p];
+    if (v == 0) {
+        bool rows = true, folds = true, same = true;
+        for (uint32_t s = b.seg_off[p]; s < b.seg_off[p + 1]; s++) {
+            rows = rows && b.row_ok[s];
+            folds = folds && b.nmt_ok[s];
+        }
+        for (uint32_t j = 0; j < 32; j++) same = same && b.got[(size_t)p * 32 + j] == b.commitments[(size_t)p * 32 + j];
+        v = !rows ? 1u : !folds ? 2u : !same ? 3u : 0u;
+    }
+    b.verdict[p] = (uint8_t)v;
+}
+
+}  // namespace
+
+int Engine::commitment_proofs_verify(const cda_commitment_proof_batch* b, uint8_t* verdict) {
+    if (!b) return fail(CDA_ERR_INVALID, "null batch");
+    const uint32_t P = b->n_proofs;
+    if (P == 0) return CDA_OK;
+    if (!verdict) return fail(CDA_ERR_INVALID, "null verdict buffer");
+    if (b->ns_len != (uint32_t)kNs)
+        return fail(CDA_ERR_INVALID, "ns_len " + std::to_string(b->ns_len) + " is not " + std::to_string(kNs));
+    if (b->threshold == 0) return fail(CDA_ERR_INVALID, "subtree root threshold must be positive");
+    if (!b->data_roots || !b->commitments || !b->seg_off)
+        return fail(CDA_ERR_INVALID, "null data_roots / commitments / seg_off");
+    if (b->seg_off[0] != 0) return fail(CDA_ERR_INVALID, at(0, "seg_off must start at 0"));
+    for (uint32_t p = 0; p < P; p++)
+        if (b->seg_off[p + 1] < b->seg_off[p]) return fail(CDA_ERR_INVALID, at(p, "seg_off decreases"));
+    const uint32_t S = b->seg_off[P];
+    if (S && (!b->nmt_start || !b->nmt_end || !b->node_off || !b->root_off || !b->row_roots || !b->rfc_total ||
+              !b->rfc_index || !b->rfc_leaf_hash || !b->aunt_off))
+        return fail(CDA_ERR_INVALID, "null segment field (nmt_start / nmt_end / node_off / root_off / row_roots / "
+                                     "rfc_total / rfc_index / rfc_leaf_hash / aunt_off)");
+    if (S && ((b->n_nodes && !b->nodes) || (b->n_roots && !b->subtree_roots) || (b->n_aunts && !b->aunts)))
+        return fail(CDA_ERR_INVALID, "null nodes / subtree_roots / aunts");
+    std::vector<uint32_t> seg_proof(S);
+    for (uint32_t p = 0; p < P; p++)
+        for (uint32_t s = b->seg_off[p]; s < b->seg_off[p + 1]; s++) seg_proof[s] = p;
+    if (S) {
+        if (b->node_off[0] != 0) return fail(CDA_ERR_INVALID, at(0, "node_off must start at 0"));
+        if (b->root_off[0] != 0) return fail(CDA_ERR_INVALID, at(0, "root_off must start at 0"));
+        if (b->aunt_off[0] != 0) return fail(CDA_ERR_INVALID, at(0, "aunt_off must start at 0"));
+    }
+    for (uint32_t s = 0; s < S; s++) {
+        const int32_t st = b->nmt_start[s], en = b->nmt_end[s];
+        auto seg = [&](const std::string& what) {
+            return fail(CDA_ERR_INVALID, at(seg_proof[s], ("segment " + std::to_string(s) + ": " + what).c_str()));
+        };
+        if (st < 0) return seg("nmt_start " + std::to_string(st) + " is negative");
+        if (en <= st) return seg("nmt_end " + std::to_string(en) + " is not above nmt_start " + std::to_string(st));
+        if (en > CDA_VERIFY_MAX_LEAVES)
+            return seg("nmt_end " + std::to_string(en) + " exceeds " + std::to_string(CDA_VERIFY_MAX_LEAVES));
+        if (b->node_off[s + 1] < b->node_off[s]) return seg("node_off decreases");
+        if (b->root_off[s + 1] < b->root_off[s]) return seg("root_off decreases");
+        if (b->aunt_off[s + 1] < b->aunt_off[s]) return seg("aunt_off decreases");
+    }
+    const uint32_t n_nodes = S ? b->n_nodes : 0, n_roots = S ? b->n_roots : 0, n_aunts = S ? b->n_aunts : 0;
+    if (S && b->node_off[S] != n_nodes)
+        return fail(CDA_ERR_INVALID, "node_off ends at " + std::to_string(b->node_off[S]) + ", n_nodes is " +
+                                         std::to_string(n_nodes));
+    if (S && b->root_off[S] != n_roots)
+        return fail(CDA_ERR_INVALID, "root_off ends at " + std::to_string(b->root_off[S]) + ", n_roots is " +
+                                         std::to_string(n_roots));
+    if (S && b->aunt_off[S] != n_aunts)
+        return fail(CDA_ERR_INVALID, "aunt_off ends at " + std::to_string(b->aunt_off[S]) + ", n_aunts is " +
+                                         std::to_string(n_aunts));
+    // "not one contiguous blob", the shape of every segment's fold and the first root of every proof
+    std::vector<uint8_t> pre(P, 0), shape(S, kShapeNotABlob);
+    std::vector<uint32_t> first_root(P + 1, 0);
+    uint32_t max_roots = 0;
+    for (uint32_t p = 0; p < P; p++) {
+        const uint32_t sa = b->seg_off[p], sb = b->seg_off[p + 1];
+        first_root[p] = sa < S ? b->root_off[sa] : n_roots;
+        first_root[p + 1] = sb < S ? b->root_off[sb] : n_roots;
+        const uint32_t roots = first_root[p + 1] - first_root[p];
+        if (roots > kMerkleRootsMaxItems)
+            return fail(CDA_ERR_INVALID, at(p, ("has " + std::to_string(roots) + " subtree roots; the limit is " +
+                                                std::to_string(kMerkleRootsMaxItems)).c_str()));
+        max_roots = std::max(max_roots, roots);
+        pre[p] = 4;
+        if (sa == sb) continue;
+        const int64_t total = b->rfc_total[sa];
+        if (total <= 0 || total % 4 || !is_pow2((uint64_t)total / 4) || total / 4 > 1024) continue;
+        const uint32_t k = (uint32_t)(total / 4);
+        bool ok = true;
+        uint64_t shares = 0;
+        for (uint32_t s = sa; s < sb && ok; s++) {
+            const int64_t idx = b->rfc_index[s];
+            ok = b->rfc_total[s] == total && idx >= 0 && idx < (int64_t)k && idx == b->rfc_index[sa] + (int64_t)(s - sa) &&
+                 (s == sa || b->nmt_start[s] == 0) && (s + 1 == sb || b->nmt_end[s] == (int32_t)k) &&
+                 b->nmt_end[s] <= (int32_t)k;
+            shares += (uint64_t)(b->nmt_end[s] - b->nmt_start[s]);
+        }
+        if (!ok) continue;
+        const uint32_t w = square::subtree_width((uint32_t)shares, b->threshold);   // shares <= k * k
+        if ((uint32_t)b->nmt_start[sa] % w) continue;
+        pre[p] = 0;
+        for (uint32_t s = sa; s < sb; s++) shape[s] = (uint8_t)(ceil_log2(w) | (ceil_log2(2 * k) << 4));
+    }
+
+    hipStream_t s = stream_;
+    // one input buffer, every array at a 16-byte boundary
+    struct Piece {
+        const void* host;
+        size_t bytes, off;
+    };
+    size_t total = 0;
+    auto piece = [&](const void* host, size_t bytes) {
+        Piece pc{host, host ? bytes : 0, total};
+        total += (pc.bytes + 15) & ~(size_t)15;
+        return pc;
+    };
+    const size_t S1 = S ? (size_t)S + 1 : 0;
+    const Piece p_dr = piece(b->data_roots, (size_t)P * 32), p_cm = piece(b->commitments, (size_t)P * 32),
+                p_seg = piece(b->seg_off, (size_t)(P + 1) * 4), p_sp = piece(seg_proof.data(), (size_t)S * 4),
+                p_st = piece(b->nmt_start, (size_t)S * 4), p_en = piece(b->nmt_end, (size_t)S * 4),
+                p_no = piece(b->node_off, S1 * 4), p_nodes = piece(b->nodes, (size_t)n_nodes * kNode),
+                p_ro = piece(b->root_off, S1 * 4), p_roots = piece(b->subtree_roots, (size_t)n_roots * kNode),
+                p_rr = piece(b->row_roots, (size_t)S * kNode), p_tot = piece(b->rfc_total, (size_t)S * 8),
+                p_idx = piece(b->rfc_index, (size_t)S * 8), p_lh = piece(b->rfc_leaf_hash, (size_t)S * 32),
+                p_ao = piece(b->aunt_off, S1 * 4), p_aunts = piece(b->aunts, (size_t)n_aunts * 32),
+                p_shape = piece(shape.data(), S), p_pre = piece(pre.data(), P),
+                p_fr = piece(first_root.data(), (size_t)(P + 1) * 4);
+    CDA_TRY(ensure(vp_in_, total + 16, "hipMalloc commitment proof batch"));
+    const size_t flags = ((size_t)S + 15) & ~(size_t)15, dig = (size_t)n_roots * 32, got = (size_t)P * 32;
+    CDA_TRY(ensure(vp_scratch_, dig + got + 2 * flags + P + 16, "hipMalloc commitment proof scratch"));
+    uint8_t* in = vp_in_.as<uint8_t>();
+    for (const Piece* pc : {&p_dr, &p_cm, &p_seg, &p_sp, &p_st, &p_en, &p_no, &p_nodes, &p_ro, &p_roots, &p_rr, &p_tot,
+                            &p_idx, &p_lh, &p_ao, &p_aunts, &p_shape, &p_pre, &p_fr})
+        if (pc->bytes) CDA_TRY(h2d(in + pc->off, pc->host, pc->bytes, s, "H2D commitment proof batch"));
+    uint8_t* scr = vp_scratch_.as<uint8_t>();
+    CommitVerify c{};
+    c.n_proofs = P;
+    c.n_segs = S;
+    c.seg_off = reinterpret_cast<const uint32_t*>(in + p_seg.off);
+    c.nmt_start = reinterpret_cast<const int32_t*>(in + p_st.off);
+    c.nmt_end = reinterpret_cast<const int32_t*>(in + p_en.off);
+    c.node_off = reinterpret_cast<const uint32_t*>(in + p_no.off);
+    c.nodes = in + p_nodes.off;
+    c.root_off = reinterpret_cast<const uint32_t*>(in + p_ro.off);
+    c.roots = in + p_roots.off;
+    c.row_roots = in + p_rr.off;
+    c.shape = in + p_shape.off;
+    c.pre = in + p_pre.off;
+    c.commitments = in + p_cm.off;
+    c.dig = reinterpret_cast<uint32_t*>(scr);
+    c.got = scr + dig;
+    c.nmt_ok = scr + dig + got;
+    c.row_ok = c.nmt_ok + flags;
+    c.verdict = c.nmt_ok + 2 * flags;
+    VerifyBatch v{};   // what vp_row_kernel reads
+    v.n_proofs = P;
+    v.n_segs = S;
+    v.ns_len = kNs;
+    v.node_len = kNode;
+    v.data_roots = in + p_dr.off;
+    v.seg_proof = reinterpret_cast<const uint32_t*>(in + p_sp.off);
+    v.row_roots = c.row_roots;
+    v.rfc_total = reinterpret_cast<const int64_t*>(in + p_tot.off);
+    v.rfc_index = reinterpret_cast<const int64_t*>(in + p_idx.off);
+    v.rfc_leaf_hash = in + p_lh.off;
+    v.aunt_off = reinterpret_cast<const uint32_t*>(in + p_ao.off);
+    v.aunts = in + p_aunts.off;
+    v.row_ok = c.nmt_ok + flags;
+    if (S) {
+        mark_begin(kStageCommitmentVerify, s);
+        hipLaunchKernelGGL(vp_row_kernel, dim3((S + 255) / 256), dim3(256), 0, s, v);
+        mark_end(s);
+        CDA_TRY(launched("commitment proof row proofs"));
+        mark_begin(kStageCommitmentVerify, s);
+        hipLaunchKernelGGL(vc_fold_kernel, dim3(S), dim3(64), 0, s, c);
+        mark_end(s);
+        CDA_TRY(launched("commitment proof row folds"));
+    }
+    mark_begin(kStageCommitmentVerify, s);
+    const hipError_t err = launch_digest_merkle_roots(c.dig, reinterpret_cast<const uint32_t*>(in + p_fr.off), P, max_roots,
+                                                      scr + dig, s);
+    mark_end(s);
+    CDA_TRY(check(err, "commitment proof commitments"));
+    mark_begin(kStageCommitmentVerify, s);
+    hipLaunchKernelGGL(vc_verdict_kernel, dim3((P + 255) / 256), dim3(256), 0, s, c);
+    mark_end(s);
+    CDA_TRY(launched("commitment proof verdicts"));
+    std::vector<uint8_t> out(P);
+    CDA_TRY(d2h(out.data(), c.verdict, P, s, "D2H verdicts"));
     CDA_TRY(sync(s));
     memcpy(verdict, out.data(), P);
     return CDA_OK;

@@ -627,6 +627,122 @@ typedef struct cda_namespace_proof_batch {
 int cda_namespace_proofs_verify(cda_ctx *ctx, uint32_t k, const uint8_t *row_roots,
                                 const cda_namespace_proof_batch *b, uint8_t *verdict);
 
+/* ---- Blob inclusion by share commitment ------------------------------------------
+ * The proof the square layout was designed for (specs/src/specs/data_square_layout.md): that the blob a
+ * PayForBlobs committed to lies in the square with a given data root, shown with the subtree roots the
+ * commitment is the Merkle root of instead of the blob's shares.  The object is celestia-node's
+ * blob.CommitmentProof (subtree roots, one NMT proof per row, the namespace, the row proof) and the per-row
+ * check nmt v0.22.0 Proof.VerifySubtreeRootInclusion, both restated from their published algorithms: no
+ * vector of theirs pins them here.  What pins this code is the reference's inclusion.GetCommitment (the
+ * Merkle root of the emitted subtree roots), block 408's PFB commitment and the DAH's row roots.
+ *
+ * A blob is (start, share_len) in row-major shares of the k x k original square.  w = SubTreeWidth(share_len,
+ * threshold); start is normalised by NextShareIndex (rounded up to a multiple of w), exactly as
+ * cda_square_blob_commitments does.  In every row it touches the blob is a leaf range [s0, e0) of the row
+ * tree, and the subtree roots of that range are its greedy aligned cover: from c = s0 the largest power of two
+ * r <= w with c % r == 0 and c + r <= e0, node c / r of level log2 r, then on from c + r
+ * (calculateSubTreeRootCoordinates).  The NMT nodes of a row are those of ProveRange(s0, e0), byte for byte
+ * what cda_square_share_proofs emits for the same range.
+ *
+ * cda_square_commitment_proofs_plan: host only, no context (the text through cda_last_error(NULL)).  Checks
+ * every blob -- share_len >= 1, the blob fits k*k after normalisation, k a power of two <= 1024, threshold >=
+ * 1, every offset of the batch fits 32 bits -- and returns the sizes to allocate.  CDA_ERR_INVALID with a
+ * message naming the blob and the field.  n == 0: CDA_OK, all sizes zero. */
+typedef struct cda_commitment_proofs_plan_t {
+    uint32_t n_segments, n_roots, n_nodes, n_aunts, aunts_per_segment;
+} cda_commitment_proofs_plan_t;
+int cda_square_commitment_proofs_plan(uint32_t k, const uint32_t *starts, const uint32_t *share_lens, uint32_t n,
+                                      uint32_t threshold, cda_commitment_proofs_plan_t *out);
+/* The proofs of n blobs.  Caller-allocated host buffers of the plan's sizes, any of them NULL (S = n_segments).
+ * The arrays carry cda_share_proofs_out's names and layouts where the meaning is the same:
+ *   seg_off n+1; nmt_start / nmt_end S; node_off S+1; nodes n_nodes*90; row_roots S*90; rfc_total / rfc_index
+ *   S; rfc_leaf_hash S*32; aunt_off S+1; aunts n_aunts*32; namespaces n*29 (the blob's first share's);
+ *   start_row / end_row n.
+ * There are no shares.  New:
+ *   root_off S+1, in roots; subtree_roots n_roots*90, packed, blob then row then left to right;
+ *   norm_start n: the normalised start;
+ *   commitments n*32 (may be NULL): the RFC-6962 root of each blob's subtree roots, equal to
+ *     cda_square_blob_commitments of the same blobs; at most 1365 subtree roots per blob (CDA_ERR_INVALID).
+ * The blobs are checked as by the plan before anything is enqueued (CDA_ERR_INVALID, outputs untouched).  One
+ * kernel launch per call, whatever n and the blobs' lengths (the kernel of cda_square_share_proofs, whose
+ * segments gather subtree roots in the place of shares); commitments costs one further launch.  Host buffers,
+ * complete when the call returns.  A square created with CDA_ERR_PUSH_ORDER answers CDA_ERR_PUSH_ORDER, outputs
+ * untouched: nmt could not have built its trees (cda_square_namespace_proofs' rule). */
+typedef struct cda_commitment_proofs_out {
+    uint32_t *seg_off;
+    int32_t *nmt_start;
+    int32_t *nmt_end;
+    uint32_t *node_off;
+    uint8_t *nodes;
+    uint8_t *row_roots;
+    int64_t *rfc_total;
+    int64_t *rfc_index;
+    uint8_t *rfc_leaf_hash;
+    uint32_t *aunt_off;
+    uint8_t *aunts;
+    uint8_t *namespaces;
+    uint32_t *start_row;
+    uint32_t *end_row;
+    uint32_t *root_off;
+    uint8_t *subtree_roots;
+    uint32_t *norm_start;
+    uint8_t *commitments;
+} cda_commitment_proofs_out;
+int cda_square_commitment_proofs(cda_square *sq, const uint32_t *starts, const uint32_t *share_lens, uint32_t n,
+                                 uint32_t threshold, const cda_commitment_proofs_out *out);
+/* The verifying side.  The batch is flat and takes any mix of proofs from squares of any width: a proof's k
+ * is rfc_total / 4 of its segments.  A proof's share count is the sum of nmt_end - nmt_start over its
+ * segments, and w = SubTreeWidth(that sum, threshold).
+ * verdict[p] (n_proofs bytes).  The order is this library's choice -- the published verifier returns on its
+ * first failure and fixes no numbering; the lowest number wins, but for 4, which needs no hashing, is decided
+ * first and wins over all:
+ *   0 valid;
+ *   4 not one contiguous blob: the proof's segments do not share one rfc_total = 4k with k a power of two <=
+ *     1024; rfc_index is not consecutive or not below k; nmt_start != 0 in a segment but the first; nmt_end
+ *     != k in a segment but the last, or nmt_end > k; the first nmt_start is not a multiple of w; the proof
+ *     has no segment;
+ *   1 a row root fails its Merkle proof against the data root (cda_share_proofs_verify's row half as is);
+ *   2 a row's subtree roots and nodes do not rebuild its row root; a subtree root count that is not the
+ *     cover's count, and too few or too many nodes for ProveRange(nmt_start, nmt_end) of the 2k-leaf tree,
+ *     are this verdict too, decided before anything is read through the counts;
+ *   3 the RFC-6962 root of the proof's subtree roots is not the claimed commitment.
+ * Checked on the host before anything is enqueued, CDA_ERR_INVALID with a message naming the proof or the
+ * segment and the field, verdict untouched (cda_share_proofs_verify's rule): null arrays; ns_len != 29;
+ * threshold == 0; offsets that do not start at 0, decrease or do not end at n_roots / n_nodes / n_aunts; not
+ * 0 <= nmt_start < nmt_end <= CDA_VERIFY_MAX_LEAVES; a proof with more than 1365 subtree roots.
+ * The fold of a row: one wavefront per segment stages its subtree roots and nodes in LDS.  The roots below
+ * level log2 w (one per set bit of the range's remainder) are one chain of hashes; the run of level log2 w
+ * folds level by level, pairs across lanes, in aligned tiles of CDA_COMMITMENT_FOLD_TILE nodes: a tile folds
+ * six levels to one node, the tiles' nodes are the next run, until one tile holds the run and folds to the
+ * root (k = 1024 with w = 1: 1024 nodes, 16 tiles, then one).
+ * Four launches per call whatever n_proofs (row proofs, row folds, commitments, verdicts), one
+ * synchronisation.  n_proofs == 0 returns CDA_OK. */
+#define CDA_COMMITMENT_FOLD_TILE 64
+typedef struct cda_commitment_proof_batch {
+    uint32_t n_proofs;
+    uint32_t ns_len;               /* 29: 90-byte nodes */
+    uint32_t threshold;            /* SubtreeRootThreshold of the squares (appconsts: 64) */
+    const uint8_t *data_roots;     /* n_proofs*32 */
+    const uint8_t *commitments;    /* n_proofs*32: the claimed share commitments */
+    const uint32_t *seg_off;       /* n_proofs+1; S = last */
+    const int32_t *nmt_start;      /* S */
+    const int32_t *nmt_end;        /* S */
+    const uint32_t *node_off;      /* S+1 */
+    const uint8_t *nodes;          /* n_nodes*90 */
+    uint32_t n_nodes;
+    const uint32_t *root_off;      /* S+1 */
+    const uint8_t *subtree_roots;  /* n_roots*90 */
+    uint32_t n_roots;
+    const uint8_t *row_roots;      /* S*90 */
+    const int64_t *rfc_total;      /* S */
+    const int64_t *rfc_index;      /* S */
+    const uint8_t *rfc_leaf_hash;  /* S*32 */
+    const uint32_t *aunt_off;      /* S+1 */
+    const uint8_t *aunts;          /* n_aunts*32, bottom-up */
+    uint32_t n_aunts;
+} cda_commitment_proof_batch;
+int cda_commitment_proofs_verify(cda_ctx *ctx, const cda_commitment_proof_batch *b, uint8_t *verdict);
+
 /* ---- Repair ------------------------------------------
  * rsmt2d ExtendedDataSquare.Repair(rowRoots, colRoots) (EXT v0.14.0,
  * go.mod:13; used by light / full nodes after sampling).  eds: w*w*512 bytes,
@@ -809,8 +925,9 @@ int cda_share_proofs_verify(cda_ctx *ctx, const cda_share_proof_batch *b, uint8_
  * enqueued stage is bracketed by events; cda_stage_times synchronises them and
  * returns, per stage, the summed milliseconds and launch counts since the
  * previous call, then resets.  Stages: 0 RS Q0 (rows+cols), 1 RS Q3, 2 push-
- * order check, 3 NMT leaves, 4 NMT levels, 5 data root. */
-#define CDA_NUM_STAGES 6
+ * order check, 3 NMT leaves, 4 NMT levels, 5 data root, 6 every launch of
+ * cda_square_commitment_proofs, 7 every launch of cda_commitment_proofs_verify. */
+#define CDA_NUM_STAGES 8
 int cda_set_profiling(cda_ctx *ctx, int enable);
 int cda_stage_times(cda_ctx *ctx, double *ms, uint32_t *counts, int n_stages);
 
