@@ -73,6 +73,7 @@ EXPORTED = (
     "cda_square_namespace_plan", "cda_square_namespace_proofs", "cda_namespace_proofs_verify",
     "cda_befp_build", "cda_befp_build_device", "cda_befp_batch_check", "cda_befp_verify",
     "cda_square_commitment_proofs_plan", "cda_square_commitment_proofs", "cda_commitment_proofs_verify",
+    "cda_repair_batch", "cda_repair_batch_device", "cda_repair_batch_plan",
 )
 # cda_namespace_proof_batch kinds (include/cda.h)
 CDA_NAMESPACE_INCLUSION = 1
@@ -119,6 +120,8 @@ class SplitLayoutT(C.Structure):
                                           "slots_bytes")]
 
 
+REPAIR_BATCH_MAX_SQUARES = 256          # CDA_REPAIR_BATCH_MAX_SQUARES
+REPAIR_BATCH_SCRATCH_BYTES = 2 << 30    # CDA_REPAIR_BATCH_SCRATCH_BYTES
 VERIFY_MAX_NS = 64         # CDA_VERIFY_MAX_NS
 VERIFY_MAX_LEAVES = 2048   # CDA_VERIFY_MAX_LEAVES
 
@@ -294,6 +297,9 @@ def load(path: str | None = None):
         L.cda_repair.argtypes = [ctxp, u8p, u8p, C.c_uint32, u8p, u8p, i32p, u32p]
         L.cda_repair_device.argtypes = [ctxp, vp, u8p, C.c_uint32, u8p, u8p, i32p, u32p]
         L.cda_rs_decode.argtypes = [ctxp, u8p, u8p, C.c_uint32, C.c_uint32, C.c_uint32]
+        L.cda_repair_batch.argtypes = [ctxp, u8p, u8p, C.c_uint32, C.c_uint32, u8p, u8p, i32p, i32p, u32p]
+        L.cda_repair_batch_device.argtypes = [ctxp, vp, u8p, C.c_uint32, C.c_uint32, u8p, u8p, i32p, i32p, u32p]
+        L.cda_repair_batch_plan.argtypes = [u8p, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u8p]
         L.cda_nmt_axis_roots.argtypes = [ctxp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u8p, i32p]
         L.cda_nmt_axis_root.argtypes = [ctxp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, u8p]
         L.cda_nmt_prove_range.argtypes = [ctxp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

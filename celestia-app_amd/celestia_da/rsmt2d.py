@@ -9,6 +9,7 @@ through libcda.so.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -235,6 +236,156 @@ class ExtendedDataSquare:
         if rc == _lib.CDA_ERR_BYZANTINE:
             raise ByzantineDataError(rc, ctx.lib.cda_last_error(ctx.h).decode(), axis.value, index.value)
         ctx.check(rc)
+
+
+@dataclass
+class RepairOutcome:
+    """What Repair made of one square of a batch: ``code`` is cda_repair's
+    (0 ok, CDA_ERR_BYZANTINE with axis / index, CDA_ERR_UNREPAIRABLE,
+    CDA_ERR_INVALID for a bad root input with its text in ``message``)."""
+    code: int
+    axis: int = -1
+    index: int = 0
+    message: str = ""
+
+    @property
+    def ok(self) -> bool:
+        return self.code == _lib.CDA_OK
+
+    @property
+    def byzantine(self) -> bool:
+        return self.code == _lib.CDA_ERR_BYZANTINE
+
+    @property
+    def unrepairable(self) -> bool:
+        return self.code == _lib.CDA_ERR_UNREPAIRABLE
+
+    @property
+    def bad_root(self) -> bool:
+        return self.code == _lib.CDA_ERR_INVALID
+
+    def error(self):
+        """The exception ExtendedDataSquare.repair raises for this outcome (None when ok)."""
+        if self.ok:
+            return None
+        if self.byzantine:
+            return ByzantineDataError(self.code, self.message, self.axis, self.index)
+        if self.unrepairable:
+            return UnrepairableError(self.code, self.message)
+        return CdaError(self.code, self.message)
+
+
+def repair_batch_chunk(w: int) -> int:
+    """Squares of width w per verification chunk of a batch repair (include/cda.h)."""
+    return min(_lib.REPAIR_BATCH_MAX_SQUARES, max(1, _lib.REPAIR_BATCH_SCRATCH_BYTES // (w * w * SHARE_SIZE)))
+
+
+def repair_batch_plan(present) -> dict:
+    """cda_repair_batch_plan (host only): the decode sweeps of a batch of
+    presence maps (n, W, W), any non-zero byte = present.  "segments": [(2 *
+    iteration + axis, (m, 3) array of square, axis, index)] in launch order;
+    "solved": (n,) bool; "iterations": the deepest square's."""
+    pres = np.ascontiguousarray(present, dtype=np.uint8)
+    if pres.ndim != 3 or pres.shape[1] != pres.shape[2]:
+        raise ValueError("present must be an (n, W, W) array")
+    n, W = pres.shape[0], pres.shape[1]
+    L = _lib.load()
+    u32p = C.POINTER(C.c_uint32)
+    n_seg = C.c_uint32(0)
+    seg_off = np.zeros(4 * W + 1, dtype=np.uint32)
+    seg_sweep = np.zeros(4 * W, dtype=np.uint32)
+    entries = np.zeros((max(n, 1) * 2 * W, 3), dtype=np.uint32)
+    solved = np.zeros(max(n, 1), dtype=np.uint8)
+    rc = L.cda_repair_batch_plan(ptr(pres) if n else None, W, n, C.byref(n_seg), seg_off.ctypes.data_as(u32p),
+                                 seg_sweep.ctypes.data_as(u32p), entries.ctypes.data_as(u32p), ptr(solved))
+    if rc != _lib.CDA_OK:
+        raise CdaError(rc, L.cda_last_error(None).decode())
+    S = n_seg.value
+    segs = [(int(seg_sweep[g]), entries[seg_off[g]:seg_off[g + 1]].copy()) for g in range(S)]
+    return {"segments": segs, "solved": solved[:n].astype(bool),
+            "iterations": (segs[-1][0] // 2 + 1) if segs else 0}
+
+
+def _batch_args(present, row_roots, col_roots, n, W):
+    pres = np.ascontiguousarray(present, dtype=np.uint8)
+    rows = np.ascontiguousarray(row_roots, dtype=np.uint8).reshape(-1)
+    cols = np.ascontiguousarray(col_roots, dtype=np.uint8).reshape(-1)
+    if pres.shape != (n, W, W):
+        raise ValueError(f"present must be ({n}, {W}, {W})")
+    if rows.size != n * W * _lib.NMT_ROOT_SIZE or cols.size != n * W * _lib.NMT_ROOT_SIZE:
+        raise ValueError("number of roots does not match the batch")
+    return pres, rows, cols
+
+
+def _batch_outcomes(ctx, rc, n, status, axis, index, single):
+    """single(i): the single-square call on square i as the batch left it, for the text of a bad root input that
+    is not the batch's first failure (the input cells are unchanged, so the replay gives the same answer)."""
+    ctx.check(rc)   # raises only when the call itself failed
+    if n == 0:
+        return []
+    first = ctx.lib.cda_last_error(ctx.h).decode()
+    out = []
+    for i in range(n):
+        code = int(status[i])
+        msg = ""
+        if code == _lib.CDA_ERR_BYZANTINE:
+            msg = f"byzantine {'row' if axis[i] == ROW else 'col'}: {index[i]}"
+        elif code == _lib.CDA_ERR_UNREPAIRABLE:
+            msg = "failed to solve data square"
+        if code != _lib.CDA_OK and first.startswith(f"square {i}: "):
+            msg = first[len(f"square {i}: "):]
+        elif code == _lib.CDA_ERR_INVALID:
+            if single(i) == code:
+                msg = ctx.lib.cda_last_error(ctx.h).decode()
+        out.append(RepairOutcome(code, int(axis[i]), int(index[i]), msg))
+    return out
+
+
+def repair_batch(eds: np.ndarray, present, row_roots, col_roots, ctx=None) -> list:
+    """cda_repair_batch: Repair of n squares of one width in one submission.
+    eds (n, W, W, 512) uint8, C-contiguous, updated in place; present (n, W,
+    W); row_roots / col_roots (n, W, 90).  Returns a RepairOutcome per square;
+    raises only when the call itself failed."""
+    ctx = ctx or default_context()
+    if eds.dtype != np.uint8 or not eds.flags.c_contiguous or eds.ndim != 4 or eds.shape[1] != eds.shape[2] \
+            or eds.shape[3] != SHARE_SIZE:
+        raise ValueError("eds must be a C-contiguous (n, W, W, 512) uint8 array")
+    n, W = eds.shape[0], eds.shape[1]
+    pres, rows, cols = _batch_args(present, row_roots, col_roots, n, W)
+    status = np.zeros(n, dtype=np.int32)
+    axis = np.full(n, -1, dtype=np.int32)
+    index = np.zeros(n, dtype=np.uint32)
+    rc = ctx.lib.cda_repair_batch(ctx.h, ptr(eds), ptr(pres), W, n, ptr(rows), ptr(cols),
+                                  status.ctypes.data_as(C.POINTER(C.c_int32)),
+                                  axis.ctypes.data_as(C.POINTER(C.c_int32)),
+                                  index.ctypes.data_as(C.POINTER(C.c_uint32)))
+    a, x = C.c_int32(-1), C.c_uint32(0)
+    return _batch_outcomes(ctx, rc, n, status, axis, index, lambda i: ctx.lib.cda_repair(
+        ctx.h, ptr(eds[i]), ptr(pres[i]), W, ptr(rows[i * W * 90:(i + 1) * W * 90]),
+        ptr(cols[i * W * 90:(i + 1) * W * 90]), C.byref(a), C.byref(x)))
+
+
+def repair_batch_device(d_eds, w: int, n: int, present, row_roots, col_roots, ctx=None) -> list:
+    """cda_repair_batch_device: as repair_batch for n squares of width w in HBM,
+    repaired in place.  d_eds: a device pointer (int) or a torch tensor on the
+    GPU holding n * w * w * 512 contiguous bytes."""
+    ctx = ctx or default_context()
+    if hasattr(d_eds, "data_ptr"):
+        if not d_eds.is_contiguous() or d_eds.numel() * d_eds.element_size() != n * w * w * SHARE_SIZE:
+            raise ValueError("the tensor must hold n * w * w * 512 contiguous bytes")
+        d_eds = d_eds.data_ptr()
+    pres, rows, cols = _batch_args(present, row_roots, col_roots, n, w)
+    status = np.zeros(n, dtype=np.int32)
+    axis = np.full(n, -1, dtype=np.int32)
+    index = np.zeros(n, dtype=np.uint32)
+    rc = ctx.lib.cda_repair_batch_device(ctx.h, d_eds, ptr(pres), w, n, ptr(rows), ptr(cols),
+                                         status.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         axis.ctypes.data_as(C.POINTER(C.c_int32)),
+                                         index.ctypes.data_as(C.POINTER(C.c_uint32)))
+    a, x = C.c_int32(-1), C.c_uint32(0)
+    return _batch_outcomes(ctx, rc, n, status, axis, index, lambda i: ctx.lib.cda_repair_device(
+        ctx.h, d_eds + i * w * w * SHARE_SIZE, ptr(pres[i]), w, ptr(rows[i * w * 90:(i + 1) * w * 90]),
+        ptr(cols[i * w * 90:(i + 1) * w * 90]), C.byref(a), C.byref(x)))
 
 
 def _fingerprint(a: np.ndarray) -> bytes:

@@ -9,6 +9,7 @@ check them in one batch and hand the cells that verified to Repair.
     batch = ResidentSquare(ods).sample_proofs(coords)      # cda_square_sample_proofs, one launch
     verdicts = verify_samples(batch, data_root)            # cda_sample_proofs_verify
     eds, present = assemble(batch, verdicts)               # -> cda_repair / rsmt2d.ExtendedDataSquare.repair
+    eds, present = assemble_batch(batches, verdicts)       # many squares -> cda_repair_batch / rsmt2d.repair_batch
 
 Reference: rsmt2d's row / column trees built by pkg/wrapper/nmt_wrapper.go
 (ErasuredNamespacedMerkleTree: Q0 cells under their own namespace, parity cells
@@ -170,4 +171,26 @@ def assemble(batch: SampleBatch, verdicts):
     r, c = batch.coords[ok, 0], batch.coords[ok, 1]
     eds[r, c] = batch.shares[ok]
     present[r, c] = 1
+    return eds, present
+
+
+def assemble_batch(batches, verdicts):
+    """(eds, present) for cda_repair_batch / rsmt2d.repair_batch: what assemble
+    builds for each square, stacked as (n, 2k, 2k, 512) and (n, 2k, 2k), so
+    that the verified samples of many heights go to one repair call.  batches:
+    one SampleBatch per square, all of one ODS width; verdicts: one verdict
+    array per batch."""
+    batches, verdicts = list(batches), list(verdicts)
+    if len(batches) != len(verdicts):
+        raise ValueError(f"{len(batches)} sample batches but {len(verdicts)} verdict arrays")
+    if not batches:
+        raise ValueError("no sample batch: the square size is unknown")
+    k = batches[0].k
+    if any(b.k != k for b in batches):
+        raise ValueError("the batches are of squares of different sizes; group them by size")
+    W, n = 2 * k, len(batches)
+    eds = np.zeros((n, W, W, SHARE_SIZE), dtype=np.uint8)
+    present = np.zeros((n, W, W), dtype=np.uint8)
+    for i, (b, v) in enumerate(zip(batches, verdicts)):
+        eds[i], present[i] = assemble(b, v)
     return eds, present

@@ -716,6 +716,50 @@ int cda_repair_device(cda_ctx* ctx, void* d_eds, const uint8_t* present, uint32_
     });
 }
 
+int cda_repair_batch_device(cda_ctx* ctx, void* d_eds, const uint8_t* present, uint32_t w, uint32_t n,
+                            const uint8_t* row_roots, const uint8_t* col_roots, int32_t* status, int32_t* byz_axis,
+                            uint32_t* byz_index) {
+    return guarded(ctx, [&](cda::Engine& e) -> int {
+        if (n == 0) return CDA_OK;
+        if (!d_eds || !present || !row_roots || !col_roots || !status) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.device_repair_batch(static_cast<uint8_t*>(d_eds), present, w, n, row_roots, col_roots, status,
+                                     byz_axis, byz_index);
+    });
+}
+
+int cda_repair_batch(cda_ctx* ctx, uint8_t* eds, const uint8_t* present, uint32_t w, uint32_t n,
+                     const uint8_t* row_roots, const uint8_t* col_roots, int32_t* status, int32_t* byz_axis,
+                     uint32_t* byz_index) {
+    return guarded(ctx, [&](cda::Engine& e) -> int {
+        if (n == 0) return CDA_OK;
+        if (!eds || !present || !row_roots || !col_roots || !status) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.host_repair_batch(eds, present, w, n, row_roots, col_roots, status, byz_axis, byz_index);
+    });
+}
+
+int cda_repair_batch_plan(const uint8_t* present, uint32_t w, uint32_t n, uint32_t* n_segments, uint32_t* seg_off,
+                          uint32_t* seg_sweep, uint32_t* entries, uint8_t* solved) {
+    // Host-only (no device work), no context.
+    return host_only(nullptr, [&](std::string* err) -> int {
+        if (w < 2 || (w & (w - 1)) || w > 1024) {
+            *err = "EDS width must be a power of two in [2, 1024]";
+            return CDA_ERR_INVALID;
+        }
+        if (n && !present) {
+            *err = "null buffer";
+            return CDA_ERR_INVALID;
+        }
+        cda::RepairPlan p;
+        cda::repair_plan(present, n, w, &p);
+        if (n_segments) *n_segments = p.n_segments();
+        if (seg_off) memcpy(seg_off, p.seg_off.data(), p.seg_off.size() * 4);
+        if (seg_sweep && p.n_segments()) memcpy(seg_sweep, p.seg_sweep.data(), p.seg_sweep.size() * 4);
+        if (entries && !p.entries.empty()) memcpy(entries, p.entries.data(), p.entries.size() * sizeof(cda::RepairEntry));
+        if (solved && n) memcpy(solved, p.solved.data(), n);
+        return CDA_OK;
+    });
+}
+
 int cda_rs_decode(cda_ctx* ctx, uint8_t* shards, const uint8_t* present, uint32_t n_shards, uint32_t shard_len,
                   uint32_t n_codewords) {
     return guarded(ctx, [&](cda::Engine& e) -> int {

@@ -13,6 +13,7 @@
 
 #include "cda_kernels.h"
 #include "hash_plan.h"
+#include "repair_plan.h"
 #include "square_plan.h"
 
 struct cda_share_proof_batch;   // include/cda.h
@@ -142,6 +143,9 @@ struct GatherPiece {
 // befp.hip: the structural checks of a fraud-proof batch, host only: "" or the first malformed field's text,
 // naming the proof and the field.
 std::string befp_batch_check(const cda_befp_batch* b);
+
+// repair.hip: squares per verification chunk of a batch repair of width w (the fixed caps of include/cda.h).
+uint32_t repair_batch_chunk(uint32_t w);
 
 // comm.hip: ncclGetUniqueId into 128 bytes (CDA_OK / CDA_ERR_DEVICE).
 int comm_unique_id(uint8_t* id);
@@ -344,6 +348,12 @@ class Engine {
     int repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present, uint32_t w, const uint8_t* row_roots,
                const uint8_t* col_roots, int32_t* byz_axis, uint32_t* byz_index);
     int host_rs_decode(uint8_t* shards, const uint8_t* present, uint32_t k, uint32_t shard_len, uint32_t n_codewords);
+    // Batch repair (repair.hip): n contiguous squares of width w, one status / axis / index per square
+    // (include/cda.h cda_repair_batch[_device]); host squares go up and come down in one copy each.
+    int host_repair_batch(uint8_t* eds, const uint8_t* present, uint32_t w, uint32_t n, const uint8_t* row_roots,
+                          const uint8_t* col_roots, int32_t* status, int32_t* byz_axis, uint32_t* byz_index);
+    int device_repair_batch(uint8_t* d_eds, const uint8_t* present, uint32_t w, uint32_t n, const uint8_t* row_roots,
+                            const uint8_t* col_roots, int32_t* status, int32_t* byz_axis, uint32_t* byz_index);
 
     // Standalone erasured NMT trees and generic RFC-6962 roots (tree.hip).
     int nmt_axis_roots(const uint8_t* cells, uint32_t cell_len, uint32_t n_cells, uint32_t n_trees,
@@ -536,6 +546,16 @@ class Engine {
     void* rp_out_ = nullptr;   // pinned landing area of repair_verify's results
     size_t rp_out_bytes_ = 0;
     uint8_t* rp_stage(const void* src, size_t n, hipStream_t s, int* rc);
+    uint8_t* rp_reserve(size_t n, hipStream_t s, int* rc);   // rp_stage without the copy: the caller fills it
+    // batch repair: the uploaded plan (entries | complete flags | expected roots) and the host plan, reused
+    DevBuf rp_batch_in_;
+    RepairPlan rp_plan_;
+    int repair_batch(uint8_t* d_eds, const uint8_t* present, uint32_t w, uint32_t n, const uint8_t* row_roots,
+                     const uint8_t* col_roots, int32_t* status, int32_t* byz_axis, uint32_t* byz_index);
+    // one verification chunk of m squares; messages[q]: the text of square q's outcome
+    int repair_batch_run(uint8_t* d_eds, const uint8_t* present, uint32_t w, uint32_t m, const uint8_t* row_roots,
+                         const uint8_t* col_roots, int32_t* status, int32_t* byz_axis, uint32_t* byz_index,
+                         std::vector<std::string>* messages);
     std::vector<uint8_t> rp_roots_;
     // standalone trees: host cells, all tree levels, axis indexes / error words, roots
     DevBuf tr_cells_, tr_levels_, tr_axis_, tr_roots_;
@@ -579,6 +599,10 @@ class Engine {
     // cells of shard_len bytes; marks them present.
     int decode_codewords(uint8_t* d_cells, uint8_t* d_present, uint32_t k, uint32_t shard_len,
                          const std::vector<uint32_t>& axis_index, hipStream_t s);
+    // The launches of it alone: n_cw descriptors already on the device, which may name any square of a batch
+    // of grids (d_cells, d_present: square 0's).
+    int decode_launch(uint8_t* d_cells, uint8_t* d_present, uint32_t k, uint32_t shard_len, const RepairEntry* d_cws,
+                      uint32_t n_cw, hipStream_t s);
 };
 
 }  // namespace cda

@@ -103,7 +103,7 @@ Engine::~Engine() {
                       &gf16_skew_, &leaf_, &lvl_, &root_slots_, &dig_, &err_buf_, &dev_err_, &h_ods_, &h_eds_,
                       &h_rows_, &h_cols_, &h_roots_, &sq_plan_, &sq_txs_, &cm_plan_, &cm_tables_,
                       &cm_leaf_, &cm_lvl_, &cm_roots_, &cm_out_, &gf8_log_, &gf8_exp_, &gf8_skew_, &rp_cw_,
-                      &rp_err_, &rp_present_, &rp_parity_, &rp_buf_, &rp_flags_, &tr_cells_, &tr_levels_,
+                      &rp_err_, &rp_present_, &rp_parity_, &rp_buf_, &rp_flags_, &rp_batch_in_, &tr_cells_, &tr_levels_,
                       &tr_axis_, &tr_roots_, &rs_pad_, &split_blk_, &split_send_, &split_col_, &split_slots_,
                       &comm_flag_, &h_par_, &vp_in_, &vp_scratch_, &bf_levels_, &bf_out_, &bf_in_, &bf_grid_})
         b->release();

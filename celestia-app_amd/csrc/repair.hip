@@ -30,6 +30,7 @@
 #include "../../include/cda.h"
 #include "engine.h"
 #include "leopard_tables.h"
+#include "repair_plan.h"
 #include "sha256_dev.h"
 
 namespace cda {
@@ -43,13 +44,14 @@ struct FieldDev {
     uint32_t bits, mod;
 };
 
-// Codeword descriptor: axis 0 = row, 1 = column; index in the EDS.
-struct Cw {
-    uint32_t axis, index;
-};
+// Codeword descriptor (repair_plan.h): square of the batch; axis 0 = row, 1 =
+// column; index in the EDS.  The single-square callers pass square 0.
+using Cw = RepairEntry;
 
-__device__ __forceinline__ uint32_t cell_off(const Cw c, uint32_t pos, uint32_t W) {
-    return c.axis == 0 ? c.index * W + pos : pos * W + c.index;
+// Cell `pos` of the codeword, in cells from the start of the batch: the offset
+// into the presence maps, and times shard_len into the cells.
+__device__ __forceinline__ size_t cell_off(const Cw c, uint32_t pos, uint32_t W) {
+    return (size_t)c.square * W * W + (c.axis == 0 ? c.index * W + pos : pos * W + c.index);
 }
 
 // errLoc[cw][i] = sum over erased work indexes j of log[i ^ j] (mod MOD).
@@ -101,10 +103,10 @@ __global__ __launch_bounds__(256) void decode_kernel(FieldDev F, const Cw* __res
     // load: work[w(p)] = received[p] * g^errLoc (erasures 0)
     for (uint32_t it = tid; it < n * S; it += nt) {
         const uint32_t p = it / S, s = it % S, w = p ^ k;
-        const uint32_t off = cell_off(c, p, W);
+        const size_t off = cell_off(c, p, W);
         uint32_t x = 0;
         if (present[off]) {
-            const uint8_t* b = eds + (size_t)off * shard_len + blk * 64;
+            const uint8_t* b = eds + off * shard_len + blk * 64;
             x = BITS == 8 ? b[s] : (uint32_t)b[s] | ((uint32_t)b[s + 32] << 8);
             x = gmul(F, x, el[w]);
         }
@@ -153,10 +155,10 @@ __global__ __launch_bounds__(256) void decode_kernel(FieldDev F, const Cw* __res
     // reveal erasures: shard = work * g^(MOD - errLoc)
     for (uint32_t it = tid; it < n * (BITS == 8 ? S : 2 * S); it += nt) {
         const uint32_t p = BITS == 8 ? it / S : it / (2 * S);
-        const uint32_t off = cell_off(c, p, W);
+        const size_t off = cell_off(c, p, W);
         if (present[off]) continue;
         const uint32_t w = p ^ k;
-        uint8_t* b = eds + (size_t)off * shard_len + blk * 64;
+        uint8_t* b = eds + off * shard_len + blk * 64;
         if (BITS == 8) {
             const uint32_t s = it % S;
             b[s] = (uint8_t)gmul(F, tmp[w * S + s], F.mod - el[w]);
@@ -209,10 +211,10 @@ __global__ __launch_bounds__(256) void decode8_kernel(const uint16_t* __restrict
     __syncthreads();
     for (uint32_t it = tid; it < n * Q; it += nt) {
         const uint32_t p = it / Q, q = it % Q, w = p ^ k;
-        const uint32_t off = cell_off(c, p, W);
+        const size_t off = cell_off(c, p, W);
         uint32_t x = 0;
         if (present[off]) {
-            x = *reinterpret_cast<const uint32_t*>(eds + (size_t)off * shard_len + blk * 64 + 4 * q);
+            x = *reinterpret_cast<const uint32_t*>(eds + off * shard_len + blk * 64 + 4 * q);
             x = mul8v(x, tab[el[w]]);
         }
         work[w * Q + q] = x;
@@ -254,10 +256,10 @@ __global__ __launch_bounds__(256) void decode8_kernel(const uint16_t* __restrict
     }
     for (uint32_t it = tid; it < n * Q; it += nt) {   // reveal erasures: work * g^(255 - errLoc)
         const uint32_t p = it / Q, q = it % Q;
-        const uint32_t off = cell_off(c, p, W);
+        const size_t off = cell_off(c, p, W);
         if (present[off]) continue;
         const uint32_t w = p ^ k;
-        *reinterpret_cast<uint32_t*>(eds + (size_t)off * shard_len + blk * 64 + 4 * q) =
+        *reinterpret_cast<uint32_t*>(eds + off * shard_len + blk * 64 + 4 * q) =
             mul8v(tmp[w * Q + q], tab[255 - el[w]]);
     }
 }
@@ -276,12 +278,13 @@ __global__ __launch_bounds__(64) void parity_compare_kernel(const uint8_t* __res
                                                             const uint8_t* __restrict__ parity, uint32_t k,
                                                             uint32_t* __restrict__ flags) {
     const uint32_t W = 2 * k, v = blockIdx.x, p = blockIdx.y;
+    const size_t sq = blockIdx.z;   // square of the batch: W * W cells, 2W * k parity shards, 2W flags each
     const uint32_t axis = v / W, i = v % W;
-    const size_t c = axis == 0 ? (size_t)i * W + k + p : (size_t)(k + p) * W + i;
+    const size_t c = sq * W * W + (axis == 0 ? (size_t)i * W + k + p : (size_t)(k + p) * W + i);
     const uint64_t* a = reinterpret_cast<const uint64_t*>(eds + c * 512);
-    const uint64_t* b = reinterpret_cast<const uint64_t*>(parity + ((size_t)v * k + p) * 512);
+    const uint64_t* b = reinterpret_cast<const uint64_t*>(parity + ((sq * 2 * W + v) * k + p) * 512);
     const bool diff = a[threadIdx.x] != b[threadIdx.x];
-    if (__any(diff) && threadIdx.x == 0) atomicOr(&flags[v], 1u);
+    if (__any(diff) && threadIdx.x == 0) atomicOr(&flags[sq * 2 * W + v], 1u);
 }
 
 // Push order of every row (blockIdx.x < k) and column with index < k: nmt
@@ -292,6 +295,8 @@ __global__ __launch_bounds__(64) void parity_compare_kernel(const uint8_t* __res
 __global__ __launch_bounds__(64) void order_kernel(const uint8_t* __restrict__ eds, uint32_t k,
                                                    uint32_t* __restrict__ flags) {
     const uint32_t W = 2 * k, axis = blockIdx.x / k, i = blockIdx.x % k;
+    const size_t sq = blockIdx.y;   // square of the batch
+    eds += sq * W * W * kShare;
     bool desc = false;
     for (uint32_t p = 1 + threadIdx.x; p < k; p += 64) {
         const size_t a = axis == 0 ? (size_t)i * W + p - 1 : (size_t)(p - 1) * W + i;
@@ -302,7 +307,28 @@ __global__ __launch_bounds__(64) void order_kernel(const uint8_t* __restrict__ e
         for (int q = 0; q < kNs && c == 0; q++) c = (int)y[q] - (int)x[q];
         desc |= c < 0;
     }
-    if (__any(desc) && threadIdx.x == 0) atomicOr(&flags[axis * W + i], 2u);
+    if (__any(desc) && threadIdx.x == 0) atomicOr(&flags[sq * 2 * W + axis * W + i], 2u);
+}
+
+// The verdict of a batch verification, one wave per vector v = (square, axis,
+// index) of n_vec = n * 2W: the computed 90-byte root against the expected one
+// (want: [n][2W][90], rows then columns of each square), with the parity and
+// order flags, for the vectors the plan says are complete at the fixed point
+// only; any of them not clean sets bit 0 of the square's word.
+constexpr uint32_t kVerdictWaves = 4;
+__global__ __launch_bounds__(64 * kVerdictWaves) void verdict_kernel(
+    const uint8_t* __restrict__ rows, const uint8_t* __restrict__ cols, const uint8_t* __restrict__ want,
+    const uint32_t* __restrict__ flags, const uint8_t* __restrict__ complete, uint32_t W, uint32_t n_vec,
+    uint32_t* __restrict__ verdict) {
+    const uint32_t v = blockIdx.x * kVerdictWaves + threadIdx.x / 64, lane = threadIdx.x % 64;
+    if (v >= n_vec) return;   // whole waves leave: v is uniform in a wave
+    if (!complete[v]) return;
+    const uint32_t sq = v / (2 * W), a = v % (2 * W), axis = a / W, i = a % W;
+    const uint8_t* got = (axis == 0 ? rows : cols) + ((size_t)sq * W + i) * kNode;
+    const uint8_t* exp = want + (size_t)v * kNode;
+    bool diff = got[lane] != exp[lane];
+    if (lane + 64 < kNode) diff |= got[lane + 64] != exp[lane + 64];
+    if ((__any(diff) || flags[v]) && lane == 0) atomicOr(&verdict[sq], 1u);
 }
 
 }  // namespace
@@ -326,7 +352,7 @@ int Engine::ensure_gf8_tables() {
 // Copies n host bytes into the pinned staging area and returns the staged
 // address (for an async H2D on s).  When the area is full, waits for s
 // (the earlier copies out of it are then done) and starts over.
-uint8_t* Engine::rp_stage(const void* src, size_t n, hipStream_t s, int* rc) {
+uint8_t* Engine::rp_reserve(size_t n, hipStream_t s, int* rc) {
     const size_t need = (n + 63) & ~(size_t)63;
     if (rp_host_used_ + need > rp_host_bytes_) {
         if ((*rc = sync(s))) return nullptr;
@@ -341,9 +367,14 @@ uint8_t* Engine::rp_stage(const void* src, size_t n, hipStream_t s, int* rc) {
         }
     }
     uint8_t* p = static_cast<uint8_t*>(rp_host_) + rp_host_used_;
-    std::memcpy(p, src, n);
     rp_host_used_ += need;
     *rc = CDA_OK;
+    return p;
+}
+
+uint8_t* Engine::rp_stage(const void* src, size_t n, hipStream_t s, int* rc) {
+    uint8_t* p = rp_reserve(n, s, rc);
+    if (p) std::memcpy(p, src, n);
     return p;
 }
 
@@ -351,8 +382,21 @@ int Engine::decode_codewords(uint8_t* d_eds, uint8_t* d_present, uint32_t k, uin
                              const std::vector<uint32_t>& axis_index, hipStream_t s) {
     const uint32_t n_cw = (uint32_t)axis_index.size() / 2;
     if (n_cw == 0) return CDA_OK;
-    const uint32_t n = 2 * k;
     int rc;
+    std::vector<Cw> cws(n_cw);
+    for (uint32_t i = 0; i < n_cw; i++) cws[i] = Cw{0, axis_index[2 * i], axis_index[2 * i + 1]};
+    CDA_TRY(ensure(rp_cw_, (size_t)n_cw * sizeof(Cw), "hipMalloc"));
+    const uint8_t* staged = rp_stage(cws.data(), (size_t)n_cw * sizeof(Cw), s, &rc);
+    if (!staged) return rc;
+    CDA_TRY(h2d(rp_cw_.ptr, staged, (size_t)n_cw * sizeof(Cw), s, "H2D"));
+    return decode_launch(d_eds, d_present, k, shard_len, rp_cw_.as<Cw>(), n_cw, s);
+}
+
+// errloc, decode and mark of n_cw codewords whose descriptors are on the
+// device (d_cws); no host wait.
+int Engine::decode_launch(uint8_t* d_eds, uint8_t* d_present, uint32_t k, uint32_t shard_len, const RepairEntry* d_cws,
+                          uint32_t n_cw, hipStream_t s) {
+    const uint32_t n = 2 * k;
     FieldDev F;
     if (k <= 128) {
         CDA_TRY(ensure_gf8_tables());
@@ -360,28 +404,24 @@ int Engine::decode_codewords(uint8_t* d_eds, uint8_t* d_present, uint32_t k, uin
     } else {
         F = FieldDev{gf16_log_.as<uint16_t>(), gf16_exp_.as<uint16_t>(), gf16_skew_.as<uint16_t>(), 16, 65535};
     }
-    CDA_TRY(ensure(rp_cw_, (size_t)n_cw * sizeof(Cw), "hipMalloc"));
     CDA_TRY(ensure(rp_err_, (size_t)n_cw * n * 2, "hipMalloc"));
-    const uint8_t* staged = rp_stage(axis_index.data(), (size_t)n_cw * sizeof(Cw), s, &rc);
-    if (!staged) return rc;
-    CDA_TRY(h2d(rp_cw_.ptr, staged, (size_t)n_cw * sizeof(Cw), s, "H2D"));
-    hipLaunchKernelGGL(errloc_kernel, dim3(n_cw), dim3(256), n * 4, s, F, rp_cw_.as<Cw>(), d_present, k,
+    hipLaunchKernelGGL(errloc_kernel, dim3(n_cw), dim3(256), n * 4, s, F, d_cws, d_present, k,
                        rp_err_.as<uint16_t>());
     CDA_TRY(launched("errloc"));
     const uint32_t S = k <= 128 ? 64 : 32;
     const size_t lds = (size_t)2 * n * S * 2;
     if (k <= 128) {
         const size_t lds8 = (1024 + 128 + (size_t)2 * n * 16) * 4;
-        hipLaunchKernelGGL(decode8_kernel, dim3(n_cw * (shard_len / 64)), dim3(256), lds8, s, F.skew, rp_cw_.as<Cw>(),
+        hipLaunchKernelGGL(decode8_kernel, dim3(n_cw * (shard_len / 64)), dim3(256), lds8, s, F.skew, d_cws,
                            d_eds, d_present, k, rp_err_.as<uint16_t>(), shard_len);
     } else {
         if (lds > 64 * 1024) CDA_TRY(check(hipFuncSetAttribute(reinterpret_cast<const void*>(decode_kernel<16>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute"));
-        hipLaunchKernelGGL(decode_kernel<16>, dim3(n_cw * (shard_len / 64)), dim3(256), lds, s, F, rp_cw_.as<Cw>(),
+        hipLaunchKernelGGL(decode_kernel<16>, dim3(n_cw * (shard_len / 64)), dim3(256), lds, s, F, d_cws,
                            d_eds, d_present, k, rp_err_.as<uint16_t>(), shard_len);
     }
     CDA_TRY(launched("decode"));
-    hipLaunchKernelGGL(mark_kernel, dim3((n_cw * n + 255) / 256), dim3(256), 0, s, rp_cw_.as<Cw>(), n_cw, d_present, n);
+    hipLaunchKernelGGL(mark_kernel, dim3((n_cw * n + 255) / 256), dim3(256), 0, s, d_cws, n_cw, d_present, n);
     return launched("mark");
 }
 
@@ -650,6 +690,204 @@ int Engine::repair(uint8_t* eds, uint8_t* d_eds, const uint8_t* present_in, uint
             return r == code ? code : r;
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// Batch repair (cda_repair_batch[_device]): n contiguous squares of one width
+// in one submission.  Per chunk of at most repair_batch_chunk(W) squares:
+//   1. the sweep plan of every square, on the host (repair_plan.h);
+//   2. two pinned uploads: the presence maps; the plan's entries, its
+//      complete-at-the-fixed-point flags and the expected roots;
+//   3. errloc, decode and mark of every segment in stream order, no host wait
+//      (errloc of sweep t + 1 sees the marks of sweep t);
+//   4. one verification of the chunk: enqueue_dah, one parity re-encode, the
+//      parity and order kernels with the square as a grid dimension, and
+//      verdict_kernel, which leaves one "not clean" word per square;
+//   5. those words back, one synchronisation.
+// A clean square is CDA_OK when the plan solved it, CDA_ERR_UNREPAIRABLE when
+// not: the same fixed point, decoded by the same kernels, and the same
+// verification as Engine::repair's fast path, so the bytes are the same too.
+// A square that is not clean goes alone through Engine::repair on its slice of
+// the batch with its own presence map: the decoder wrote erased cells only, so
+// every input cell is still in place and the replay ignores and overwrites
+// the rest.
+// ---------------------------------------------------------------------------
+uint32_t repair_batch_chunk(uint32_t W) {
+    const uint64_t eds_b = (uint64_t)W * W * kShare;
+    const uint64_t by_bytes = std::max<uint64_t>(1, (uint64_t)CDA_REPAIR_BATCH_SCRATCH_BYTES / eds_b);
+    return (uint32_t)std::min<uint64_t>(CDA_REPAIR_BATCH_MAX_SQUARES, by_bytes);
+}
+
+namespace {
+
+// An outcome of Repair for one square, as opposed to a call that could not run.
+bool repair_outcome(int rc, const std::string& msg) {
+    return rc == CDA_OK || rc == CDA_ERR_BYZANTINE || rc == CDA_ERR_UNREPAIRABLE ||
+           (rc == CDA_ERR_INVALID && msg.rfind("bad root input", 0) == 0);
+}
+
+size_t pad16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+}  // namespace
+
+int Engine::repair_batch_run(uint8_t* E, const uint8_t* present_in, uint32_t W, uint32_t m, const uint8_t* row_roots,
+                             const uint8_t* col_roots, int32_t* status, int32_t* byz_axis, uint32_t* byz_index,
+                             std::vector<std::string>* messages) {
+    const uint32_t k = W / 2, SH = kShare;
+    const size_t cells = (size_t)W * W, eds_b = cells * SH, roots_b = (size_t)W * kNode, n_vec = (size_t)m * 2 * W;
+    hipStream_t s = stream_;
+    int rc;
+    // earlier copies out of the staging area are done once s is idle
+    CDA_TRY(sync(s));
+    rp_host_used_ = 0;
+    // ---- plan and uploads
+    CDA_TRY(ensure(rp_present_, m * cells, "hipMalloc"));
+    uint8_t* pres = rp_reserve(m * cells, s, &rc);
+    if (!pres) return rc;
+    RepairPlan& plan = rp_plan_;
+    repair_plan(present_in, m, W, &plan, pres);
+    CDA_TRY(h2d(rp_present_.ptr, pres, m * cells, s, "H2D"));
+    const size_t ent_b = pad16(plan.entries.size() * sizeof(Cw)), comp_b = pad16(n_vec), want_b = n_vec * kNode;
+    CDA_TRY(ensure(rp_batch_in_, ent_b + comp_b + want_b, "hipMalloc"));
+    uint8_t* in = rp_reserve(ent_b + comp_b + want_b, s, &rc);
+    if (!in) return rc;
+    if (!plan.entries.empty()) std::memcpy(in, plan.entries.data(), plan.entries.size() * sizeof(Cw));
+    std::memcpy(in + ent_b, plan.complete.data(), n_vec);
+    for (uint32_t q = 0; q < m; q++) {
+        std::memcpy(in + ent_b + comp_b + (size_t)q * 2 * roots_b, row_roots + q * roots_b, roots_b);
+        std::memcpy(in + ent_b + comp_b + (size_t)q * 2 * roots_b + roots_b, col_roots + q * roots_b, roots_b);
+    }
+    CDA_TRY(h2d(rp_batch_in_.ptr, in, ent_b + comp_b + want_b, s, "H2D"));
+    const Cw* d_entries = rp_batch_in_.as<Cw>();
+    const uint8_t* d_complete = rp_batch_in_.as<uint8_t>() + ent_b;
+    const uint8_t* d_want = d_complete + comp_b;
+    // ---- every sweep of every square
+    CDA_TRY(ensure(rp_err_, (size_t)plan.max_segment * W * 2, "hipMalloc"));
+    for (uint32_t g = 0; g < plan.n_segments(); g++)
+        CDA_TRY(decode_launch(E, rp_present_.as<uint8_t>(), k, SH, d_entries + plan.seg_off[g],
+                              plan.seg_off[g + 1] - plan.seg_off[g], s));
+    // ---- verification, the verdict staying on the device
+    CDA_TRY(ensure(rp_parity_, (size_t)m * 2 * W * k * SH, "hipMalloc"));
+    CDA_TRY(ensure(rp_flags_, (n_vec + m) * 4, "hipMalloc"));
+    CDA_TRY(ensure(h_rows_, m * roots_b, "hipMalloc"));
+    CDA_TRY(ensure(h_cols_, m * roots_b, "hipMalloc"));
+    CDA_TRY(ensure(err_buf_, (size_t)m * 4, "hipMalloc"));
+    CDA_TRY(enqueue_dah(E, k, m, h_rows_.as<uint8_t>(), h_cols_.as<uint8_t>(), nullptr, err_buf_.as<uint32_t>(),
+            nullptr, s));
+    RsJob j{};
+    j.src = E;
+    j.dst = rp_parity_.as<uint8_t>();
+    j.src_sq = eds_b;
+    j.dst_sq = (uint64_t)2 * W * k * SH;
+    j.n_seg = 2;
+    j.seg[0] = RsSeg{W, 0, W * SH, SH, 0, k * SH, SH};              // rows: data half = cells 0..k-1
+    j.seg[1] = RsSeg{W, 0, SH, W * SH, W * k * SH, k * SH, SH};     // columns
+    CDA_TRY(check(launch_rs(j, k, m, gf16(k), s), "parity re-encode"));
+    uint32_t* d_flags = rp_flags_.as<uint32_t>();
+    uint32_t* d_verdict = d_flags + n_vec;
+    CDA_TRY(fill(d_flags, 0, (n_vec + m) * 4, s, "hipMemsetAsync"));
+    hipLaunchKernelGGL(parity_compare_kernel, dim3(2 * W, k, m), dim3(64), 0, s, E, rp_parity_.as<uint8_t>(), k,
+                       d_flags);
+    CDA_TRY(launched("parity compare"));
+    hipLaunchKernelGGL(order_kernel, dim3(2 * k, m), dim3(64), 0, s, E, k, d_flags);
+    CDA_TRY(launched("push order"));
+    hipLaunchKernelGGL(verdict_kernel, dim3((uint32_t)((n_vec + kVerdictWaves - 1) / kVerdictWaves)),
+                       dim3(64 * kVerdictWaves), 0, s, h_rows_.as<uint8_t>(), h_cols_.as<uint8_t>(), d_want, d_flags,
+                       d_complete, W, (uint32_t)n_vec, d_verdict);
+    CDA_TRY(launched("repair verdict"));
+    const size_t out_b = (size_t)m * 4;
+    if (out_b > rp_out_bytes_) {
+        if (rp_out_) (void)hipHostFree(rp_out_);
+        rp_out_ = nullptr;
+        rp_out_bytes_ = 0;
+        CDA_TRY(check(hipHostMalloc(&rp_out_, out_b, hipHostMallocDefault), "hipHostMalloc"));
+        rp_out_bytes_ = out_b;
+    }
+    CDA_TRY(d2h(rp_out_, d_verdict, out_b, s, "D2H"));
+    CDA_TRY(sync(s));
+    const std::vector<uint32_t> verdict(static_cast<const uint32_t*>(rp_out_), static_cast<const uint32_t*>(rp_out_) + m);
+    const std::vector<uint8_t>& solved = plan.solved;
+    // ---- outcomes; the squares that are not clean alone through the single-square path
+    for (uint32_t q = 0; q < m; q++) {
+        byz_axis[q] = -1;
+        byz_index[q] = 0;
+        (*messages)[q].clear();
+        if (verdict[q] == 0) {
+            status[q] = solved[q] ? CDA_OK : CDA_ERR_UNREPAIRABLE;
+            if (!solved[q]) (*messages)[q] = "failed to solve data square";
+            continue;
+        }
+        err_.clear();
+        const int r = repair(nullptr, E + q * eds_b, present_in + q * cells, W, row_roots + q * roots_b,
+                             col_roots + q * roots_b, &byz_axis[q], &byz_index[q]);
+        if (!repair_outcome(r, err_)) return r;   // the call itself failed
+        status[q] = r;
+        (*messages)[q] = err_;
+    }
+    return CDA_OK;
+}
+
+// d_eds: n contiguous squares in HBM.  status / byz_axis / byz_index are
+// written only when every square received a status.
+int Engine::repair_batch(uint8_t* d_eds, const uint8_t* present, uint32_t W, uint32_t n, const uint8_t* row_roots,
+                         const uint8_t* col_roots, int32_t* status, int32_t* byz_axis, uint32_t* byz_index) {
+    const uint32_t k = W / 2;
+    if (W < 2 || (W & (W - 1)) || k > 512) return fail(CDA_ERR_INVALID, "EDS width must be a power of two in [2, 1024]");
+    const size_t cells = (size_t)W * W, eds_b = cells * kShare, roots_b = (size_t)W * kNode;
+    std::vector<int32_t> st(n, CDA_OK), ax(n, -1);
+    std::vector<uint32_t> ix(n, 0);
+    std::vector<std::string> msg(n);
+    const uint32_t chunk = repair_batch_chunk(W);
+    for (uint32_t i0 = 0; i0 < n; i0 += chunk) {
+        const uint32_t m = std::min(chunk, n - i0);
+        std::vector<std::string> part(m);
+        CDA_TRY(repair_batch_run(d_eds + i0 * eds_b, present + i0 * cells, W, m, row_roots + i0 * roots_b,
+                                 col_roots + i0 * roots_b, &st[i0], &ax[i0], &ix[i0], &part));
+        for (uint32_t q = 0; q < m; q++) msg[i0 + q] = std::move(part[q]);
+    }
+    err_.clear();
+    for (uint32_t i = n; i-- > 0;)
+        if (st[i] != CDA_OK) err_ = "square " + std::to_string(i) + ": " + msg[i];   // ends on the lowest
+    for (uint32_t i = 0; i < n; i++) {
+        status[i] = st[i];
+        if (byz_axis) byz_axis[i] = ax[i];
+        if (byz_index) byz_index[i] = ix[i];
+    }
+    return CDA_OK;
+}
+
+int Engine::device_repair_batch(uint8_t* d_eds, const uint8_t* present, uint32_t W, uint32_t n,
+                                const uint8_t* row_roots, const uint8_t* col_roots, int32_t* status,
+                                int32_t* byz_axis, uint32_t* byz_index) {
+    // the squares may have been written on any stream of the caller
+    CDA_TRY(check(hipDeviceSynchronize(), "hipDeviceSynchronize"));
+    return repair_batch(d_eds, present, W, n, row_roots, col_roots, status, byz_axis, byz_index);
+}
+
+// One upload and one download of the whole batch, the caller's buffer
+// page-locked for the call as the batch extension does.
+int Engine::host_repair_batch(uint8_t* eds, const uint8_t* present, uint32_t W, uint32_t n, const uint8_t* row_roots,
+                              const uint8_t* col_roots, int32_t* status, int32_t* byz_axis, uint32_t* byz_index) {
+    const uint32_t k = W / 2;
+    if (W < 2 || (W & (W - 1)) || k > 512) return fail(CDA_ERR_INVALID, "EDS width must be a power of two in [2, 1024]");
+    const size_t b = (size_t)n * W * W * kShare;
+    hipStream_t s = stream_;
+    CDA_TRY(ensure(h_eds_, b, "hipMalloc"));
+    HostPin pin(host_register_, eds, b, stream_, copy_out_);
+    CDA_TRY(h2d(h_eds_.ptr, eds, b, s, "H2D"));
+    std::vector<int32_t> st(n), ax(n);
+    std::vector<uint32_t> ix(n);
+    CDA_TRY(repair_batch(h_eds_.as<uint8_t>(), present, W, n, row_roots, col_roots, st.data(), ax.data(), ix.data()));
+    const std::string text = err_;
+    CDA_TRY(d2h(eds, h_eds_.ptr, b, s, "D2H"));
+    CDA_TRY(sync(s));
+    err_ = text;
+    for (uint32_t i = 0; i < n; i++) {
+        status[i] = st[i];
+        if (byz_axis) byz_axis[i] = ax[i];
+        if (byz_index) byz_index[i] = ix[i];
+    }
+    return CDA_OK;
 }
 
 int Engine::host_rs_decode(uint8_t* shards, const uint8_t* present, uint32_t k, uint32_t shard_len,

@@ -32,6 +32,9 @@
  *   cda_blob_commitments   go-square inclusion.CreateCommitment
  *                          (x/blob/types/blob_tx.go:98, payforblob.go:53)
  *   cda_repair             rsmt2d ExtendedDataSquare.Repair (EXT v0.14.0)
+ *   cda_repair_batch / cda_repair_batch_device / cda_repair_batch_plan
+ *                          Repair of many squares of one width in one
+ *                          submission, every sweep planned on the host first
  *   cda_rs_decode          rsmt2d Codec.Decode (reedsolomon Reconstruct)
  *   cda_square_*           resident squares: proof.NewShareInclusionProofFromEDS
  *                          (pkg/proof/proof.go:77), inclusion.GetCommitment
@@ -762,6 +765,70 @@ int cda_repair(cda_ctx *ctx, uint8_t *eds, const uint8_t *present, uint32_t w, c
  * device and complete when the call returns. */
 int cda_repair_device(cda_ctx *ctx, void *d_eds, const uint8_t *present, uint32_t w, const uint8_t *row_roots,
                       const uint8_t *col_roots, int32_t *byz_axis, uint32_t *byz_index);
+/* ---- Batch repair --------------------------------------------------------------
+ * cda_repair_device for n contiguous squares of one width in one submission
+ * (a node catching up over a range of heights).  d_eds: n * w*w*512 device
+ * bytes, repaired in place; present: n * w*w host bytes (any non-zero byte =
+ * present); row_roots / col_roots: n * w*90 host bytes each.  status[n],
+ * byz_axis[n] (may be NULL), byz_index[n] (may be NULL): written per square
+ * with the codes cda_repair returns; byz_axis is -1 where none.
+ *
+ * Which vectors become decodable in which sweep depends on the presence maps
+ * alone, so every sweep of every square is planned on the host before the
+ * first launch (cda_repair_batch_plan), uploaded once, and the decode
+ * launches of all squares follow each other with no host wait.  One
+ * verification per chunk of squares leaves one word per square on the device;
+ * only those words come back.  The batch is processed in chunks of
+ * min(CDA_REPAIR_BATCH_MAX_SQUARES, CDA_REPAIR_BATCH_SCRATCH_BYTES /
+ * (w*w*512)) squares, at least one: the verification's scratch is one
+ * EDS-size per square of a chunk.  One synchronisation per chunk.
+ * A square whose verification is not clean (byzantine, bad root input) is then
+ * run alone through cda_repair_device's path on its slice of the batch, which
+ * gives that call's outcome, axis, index and message.
+ *
+ * Returns CDA_OK whenever every square received a status, whatever the
+ * statuses are; another code only when the call itself could not run (a width
+ * that is not a power of two in [2, 1024]: CDA_ERR_INVALID; a device error),
+ * and status / byz_axis / byz_index are then left untouched.  cda_last_error
+ * holds the message of the lowest-numbered square whose status is not CDA_OK,
+ * prefixed "square <i>: " (empty when there is none).  n == 0 returns CDA_OK.
+ *
+ * The bytes of square i afterwards:
+ *   CDA_OK, or CDA_ERR_UNREPAIRABLE: byte-equal to what cda_repair_device
+ *     leaves for that square alone;
+ *   CDA_ERR_BYZANTINE, CDA_ERR_INVALID: every cell present in the input is
+ *     unchanged, and every cell cda_repair_device's replay writes holds the
+ *     bytes that call writes; other absent cells are unspecified (they may
+ *     hold the batch sweeps' decode).
+ * cda_repair_batch: the same for host squares (eds: n * w*w*512 host bytes),
+ * with one upload and one download of the whole batch through a page-locked
+ * view of the caller's buffer, as cda_extend_dah_batch does. */
+#define CDA_REPAIR_BATCH_MAX_SQUARES 256
+#define CDA_REPAIR_BATCH_SCRATCH_BYTES (2ull << 30)
+int cda_repair_batch_device(cda_ctx *ctx, void *d_eds, const uint8_t *present, uint32_t w, uint32_t n,
+                            const uint8_t *row_roots, const uint8_t *col_roots, int32_t *status, int32_t *byz_axis,
+                            uint32_t *byz_index);
+int cda_repair_batch(cda_ctx *ctx, uint8_t *eds, const uint8_t *present, uint32_t w, uint32_t n,
+                     const uint8_t *row_roots, const uint8_t *col_roots, int32_t *status, int32_t *byz_axis,
+                     uint32_t *byz_index);
+/* The sweep plan of such a batch, host only, no context (the text through
+ * cda_last_error(NULL)).  Per square, in each iteration every incomplete row
+ * with >= w/2 cells is decoded, then, with the counts updated, every such
+ * column, until nothing is decodable or every cell is present.  The plan is
+ * one list of (square, axis, index) entries cut into segments in launch order
+ * -- iteration 0 rows, iteration 0 columns, iteration 1 rows, ... -- each
+ * holding the entries of all squares, squares ascending; empty segments are
+ * dropped.  Outputs, caller-allocated, any of them NULL:
+ *   *n_segments;
+ *   seg_off    4w+1 words: segment g owns entries [seg_off[g], seg_off[g+1]);
+ *   seg_sweep  4w words: 2 * iteration + axis of segment g, ascending;
+ *   entries    n * 2w * 3 words: square, axis (0 row / 1 column), index;
+ *   solved     n bytes: 1 when every cell of the square is present at the end.
+ * At most 4w segments and 2w entries per square exist.  n == 0: CDA_OK, no
+ * segments.  CDA_ERR_INVALID for a width that is not a power of two in
+ * [2, 1024]. */
+int cda_repair_batch_plan(const uint8_t *present, uint32_t w, uint32_t n, uint32_t *n_segments, uint32_t *seg_off,
+                          uint32_t *seg_sweep, uint32_t *entries, uint8_t *solved);
 /* rsmt2d Codec.Decode (LeoRSCodec -> reedsolomon Reconstruct): n_codewords
  * codewords of 2*n_shards shards of shard_len bytes (multiple of 64),
  * contiguous; shards with present[] == 0 are reconstructed in place (data
