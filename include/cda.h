@@ -83,6 +83,22 @@
  *     caller's stream; their GPU work is ordered after the previous call's on
  *     the same context (any stream), because the context's scratch is shared.
  *     Use one context per device.
+ *   - Alignment of device pointers.  A device pointer must be aligned to the
+ *     widest access a kernel makes straight through it (host buffers need only
+ *     their element type's alignment).  The library does not check this: a
+ *     pointer below its alignment is the caller's error.  The values,
+ *     repeated at each argument below:
+ *       16  share buffers (d_ods, d_eds, d_ods_rows, d_row_block, d_col_block,
+ *           d_send) and arrays of 96-byte node slots (d_col_root_slots,
+ *           d_row_subtree_slots): 16-byte loads and stores;
+ *        8  d_ods of cda_square_construct_device: the share writer stores 8
+ *           bytes per lane;
+ *        4  32-byte digests (d_data_roots, d_data_root, d_commitments), the
+ *           status and push-order words (d_status, d_err), and the byte
+ *           buffers d_txs / d_data (read as 4-byte words from the pointer);
+ *        2  packed 90-byte roots (d_row_roots, d_col_roots): 2-byte stores.
+ *     The layouts' strides (512, 96, 90, 32, 4) keep every element of a batch
+ *     at the alignment of the first.
  */
 #ifndef CDA_H
 #define CDA_H
@@ -181,7 +197,10 @@ int cda_extend_dah_batch_ex(cda_ctx *ctx, const uint8_t *ods, uint32_t k, uint32
  * PyTorch/Go caller enqueues on by default -- NOT the context's private
  * stream, so the call is ordered after the caller's own work. Asynchronous: the
  * call only enqueues work. Per-square push-order status is written to d_status
- * (n int32, device memory, may be NULL). */
+ * (n int32, device memory, may be NULL).
+ * Alignment: d_ods, d_eds 16 bytes; d_row_roots, d_col_roots 2; d_data_roots
+ * 4; d_status 4.  d_ods is read only; exactly n*(2k)^2*512, n*2k*90 (twice),
+ * n*32 and n*4 bytes are written. */
 int cda_extend_dah_device(cda_ctx *ctx, const void *d_ods, uint32_t k, uint32_t n, void *d_eds, void *d_row_roots,
                           void *d_col_roots, void *d_data_roots, int32_t *d_status, void *stream);
 
@@ -198,7 +217,10 @@ int cda_reserve(cda_ctx *ctx, uint32_t k, uint32_t n);
  * the layout rsmt2d's EDS has after ExtendShares.  The cgo caller flattens the
  * [][]byte shares straight into that arena (it must copy them into one flat
  * buffer anyway), so the kernels read Q0 where it lies and never copy it.
- * Outputs and semantics are identical to cda_extend_dah_device. */
+ * Outputs and semantics are identical to cda_extend_dah_device; Q0 of d_eds is
+ * read only, the three parity quadrants are written.
+ * Alignment: d_eds 16 bytes; d_row_roots, d_col_roots 2; d_data_roots 4;
+ * d_status 4. */
 int cda_extend_dah_inplace_device(cda_ctx *ctx, uint32_t k, uint32_t n, void *d_eds, void *d_row_roots,
                                   void *d_col_roots, void *d_data_roots, int32_t *d_status, void *stream);
 
@@ -240,7 +262,10 @@ int cda_push_order_detail_at(cda_ctx *ctx, uint32_t square, int32_t *axis, uint3
  *  4. caller: gather the subtree slots ([G][W][96]) and column root slots
  *     ([W][96], rank order) on one rank.
  *  5. cda_split_combine: top log2(G) levels of every row tree, pack roots,
- *     data root. */
+ *     data root.
+ * Alignment: d_ods_rows, d_row_block, d_col_block, d_send 16 bytes;
+ * d_col_root_slots, d_row_subtree_slots 16; d_err 4 (exactly one word is
+ * written); d_row_roots, d_col_roots 2; d_data_root 4. */
 int cda_split_rows(cda_ctx *ctx, const void *d_ods_rows, uint32_t k, uint32_t n_rows, uint32_t row0,
                    void *d_row_block, uint32_t *d_err, void *stream);
 int cda_split_cols(cda_ctx *ctx, void *d_col_block, uint32_t k, uint32_t n_cols, uint32_t col0,
@@ -264,7 +289,9 @@ int cda_split_combine(cda_ctx *ctx, const void *d_row_subtree_slots, uint32_t pa
  *   d_row_roots / d_col_roots (W*90) / d_data_root (32): rank 0 only;
  *   d_err: one device uint32, on rank 0 the MIN over ranks of the push-order
  *     words (0xFFFFFFFF = ordered; axis<<24 | index<<12 | position; 0 = a rank
- *     failed locally: rank 0 then returns CDA_ERR_DEVICE and writes no roots). */
+ *     failed locally: rank 0 then returns CDA_ERR_DEVICE and writes no roots).
+ * Alignment: d_ods_rows, d_col_block 16 bytes; d_row_roots, d_col_roots 2;
+ * d_data_root 4; d_err 4. */
 #define CDA_COMM_ID_BYTES 128
 int cda_comm_unique_id(uint8_t id[CDA_COMM_ID_BYTES]);
 int cda_comm_init(cda_ctx *ctx, int rank, int world, const uint8_t id[CDA_COMM_ID_BYTES]);
@@ -292,7 +319,8 @@ int cda_extend_dah_split(cda_ctx *ctx, const void *d_ods_rows, uint32_t k, void 
 /* Step 1 of the split for a caller that runs its own all-to-all (e.g. over
  * torch.distributed): the row block of R ODS rows written straight in the send
  * layout [parts][R][C][512] (part h = columns [h*C, h*C + C)), so the received
- * pieces ARE rows 0..k-1 of the receiver's column block. */
+ * pieces ARE rows 0..k-1 of the receiver's column block.
+ * Alignment: d_ods_rows, d_send 16 bytes; d_err 4. */
 int cda_split_rows_send(cda_ctx *ctx, const void *d_ods_rows, uint32_t k, uint32_t n_rows, uint32_t row0,
                         uint32_t parts, void *d_send, uint32_t *d_err, void *stream);
 /* The split's buffer arithmetic (host only, no context; csrc/split_layout.h,
@@ -395,7 +423,10 @@ int cda_construct_extend_dah(cda_ctx *ctx, const uint8_t *txs, const uint64_t *t
 /* Device variant: the layout is planned from the host txs, the shares are
  * written from d_txs (a device copy of the same bytes with >= 16 readable
  * bytes after the end) into d_ods; only enqueues on stream (NULL = HIP's
- * default stream). */
+ * default stream).  The bytes read after the end never reach the shares: a
+ * blob's last share is zero-padded whatever follows d_txs.  Of d_ods exactly
+ * square_size^2 * 512 bytes are written, whatever ods_capacity is.
+ * Alignment: d_txs 4 bytes; d_ods 8. */
 int cda_square_construct_device(cda_ctx *ctx, const uint8_t *txs, const uint64_t *tx_off, uint32_t n_txs,
                                 const void *d_txs, uint32_t max_square_size, uint32_t threshold, int mode,
                                 void *d_ods, size_t ods_capacity, uint32_t *square_size, uint32_t *kept,
@@ -417,7 +448,9 @@ int cda_blob_commitments(cda_ctx *ctx, const uint8_t *namespaces, const uint8_t 
 /* Device variant: d_data is a device copy of the blob bytes with >= 16
  * readable bytes after the end, d_commitments is device memory; namespaces /
  * offsets / versions stay on the host (the layout is planned there).  Only
- * enqueues on stream (NULL = HIP's default stream). */
+ * enqueues on stream (NULL = HIP's default stream).  The bytes read after the
+ * end never reach a commitment.
+ * Alignment: d_data 4 bytes; d_commitments 4 (n*32 bytes written). */
 int cda_blob_commitments_device(cda_ctx *ctx, const uint8_t *namespaces, const uint64_t *data_off,
                                 const uint8_t *share_versions, uint32_t n, uint32_t threshold, const void *d_data,
                                 void *d_commitments, void *stream);
@@ -762,13 +795,14 @@ int cda_repair(cda_ctx *ctx, uint8_t *eds, const uint8_t *present, uint32_t w, c
 /* cda_repair on an HBM-resident square (d_eds: w*w*512 device bytes, repaired
  * in place; present and the roots stay host buffers).  Same outcomes and
  * messages; the work is ordered after everything already queued on the
- * device and complete when the call returns. */
+ * device and complete when the call returns.  Cells present in the input are
+ * never written, whatever the outcome.  Alignment: d_eds 16 bytes. */
 int cda_repair_device(cda_ctx *ctx, void *d_eds, const uint8_t *present, uint32_t w, const uint8_t *row_roots,
                       const uint8_t *col_roots, int32_t *byz_axis, uint32_t *byz_index);
 /* ---- Batch repair --------------------------------------------------------------
  * cda_repair_device for n contiguous squares of one width in one submission
  * (a node catching up over a range of heights).  d_eds: n * w*w*512 device
- * bytes, repaired in place; present: n * w*w host bytes (any non-zero byte =
+ * bytes (16-byte aligned), repaired in place; present: n * w*w host bytes (any non-zero byte =
  * present); row_roots / col_roots: n * w*90 host bytes each.  status[n],
  * byz_axis[n] (may be NULL), byz_index[n] (may be NULL): written per square
  * with the codes cda_repair returns; byz_axis is -1 where none.
@@ -859,8 +893,10 @@ int cda_rs_decode(cda_ctx *ctx, uint8_t *shards, const uint8_t *present, uint32_
  * cells, positions ascending, every proof against the orthogonal root;
  * *n_out their count, which may be below k -- the caller decides what then.
  * The launches do not grow with w but for the log2 w tree levels; one
- * synchronisation per call.  _device: d_eds in HBM, complete before the call
- * (as cda_repair_device leaves it); the other buffers stay host buffers. */
+ * synchronisation per call.  _device: d_eds in HBM (16-byte aligned, read
+ * only), complete before the call (as cda_repair_device leaves it); the other
+ * buffers stay host buffers.  Of positions, shares and nmt_nodes only the first
+ * *n_out entries are written. */
 int cda_befp_build(cda_ctx *ctx, const uint8_t *eds, uint32_t w, int axis, uint32_t index,
                    const uint8_t *row_roots, const uint8_t *col_roots, uint32_t *n_out, uint32_t *positions,
                    uint8_t *shares, uint8_t *nmt_nodes);

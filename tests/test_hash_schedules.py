@@ -27,6 +27,7 @@ import re
 import numpy as np
 import pytest
 
+import guarded
 import hash_plan_tool as hp
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -285,17 +286,24 @@ def test_sweep_batch_matches_oracle(ctx, k, n):
     bad_j = 2 if n >= 4 and k >= 2 else None
     dev = torch.device("cuda", 0)
     exp = [_expected(k, j, j == bad_j) for j in range(d)]
-    eds = rows = cols = roots = status = None
+    eds = rows = cols = roots = status = guards = None
     try:
         eds = torch.zeros((n, W, W, 512), dtype=torch.uint8, device=dev)
         for j in range(d):
             eds[j::d, :k, :k] = torch.from_numpy(exp[j][0]).to(dev).view(k, k, 512)
-        rows = torch.empty(n, W * 90, dtype=torch.uint8, device=dev)
-        cols = torch.empty(n, W * 90, dtype=torch.uint8, device=dev)
-        roots = torch.empty(n, 32, dtype=torch.uint8, device=dev)
-        status = torch.full((n,), 77, dtype=torch.int32, device=dev)
-        ctx.extend_dah_inplace_device(k, n, eds.data_ptr(), rows.data_ptr(), cols.data_ptr(), roots.data_ptr(),
-                                      status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        # The kernel that stores the packed roots, the data roots and the
+        # status words depends on the plan class, so these four lie in guarded
+        # buffers (tests/guarded.py), each at exactly its documented minimum
+        # alignment: an unwritten byte still holds the pattern and fails the
+        # comparisons below, a store next to a buffer fails its guards.
+        guards = [guarded.alloc(n * W * 90, stride=W * 90, align=2, backend="torch", name="d_row_roots"),
+                  guarded.alloc(n * W * 90, stride=W * 90, align=2, backend="torch", name="d_col_roots"),
+                  guarded.alloc(n * 32, stride=32, align=4, backend="torch", name="d_data_roots"),
+                  guarded.alloc(n * 4, stride=4, align=4, backend="torch", name="d_status")]
+        rows, cols = guards[0].payload().view(n, W * 90), guards[1].payload().view(n, W * 90)
+        roots, status = guards[2].payload().view(n, 32), guards[3].payload().view(torch.int32)
+        ctx.extend_dah_inplace_device(k, n, eds.data_ptr(), *[g.ptr for g in guards],
+                                      torch.cuda.current_stream(dev).cuda_stream)
         torch.cuda.synchronize()
 
         def check(which, got, want, j):
@@ -338,6 +346,8 @@ def test_sweep_batch_matches_oracle(ctx, k, n):
                 assert ctx.push_order_detail_at(i) == exp[bad_j][5], f"k={k} n={n} i={i}: push-order detail"
         assert ctx.push_order_detail_at(0) == (-1, 0, 0) and ctx.push_order_detail_at(n - 1) == (
             exp[(n - 1) % d][5]), f"k={k} n={n}: push-order detail of the first / last square"
+        for g in guards:
+            g.assert_guards(f"k={k} n={n} {g.name}")
     finally:
-        del eds, rows, cols, roots, status
+        del eds, rows, cols, roots, status, guards
         torch.cuda.empty_cache()

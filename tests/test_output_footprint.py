@@ -1,0 +1,1158 @@
+"""The footprint of every caller-owned buffer: what an entry point writes, and
+nothing next to it.
+
+The other GPU tests give each output an allocation of its own, so a store a
+few bytes before or after it lands in allocator slack that nobody reads.  Here
+every output and every const input lies inside a guarded buffer
+(tests/guarded.py): one allocation of lead | payload | trail filled with a
+position-dependent pattern.  Each case asserts three things together:
+
+  payload  equals the reference (the C oracle, pyref, or the committed
+           restatements in tests/), and the pattern where include/cda.h says
+           the call leaves bytes alone;
+  guards   lead and trail of every buffer still hold the pattern;
+  inputs   every const input is byte-identical afterwards.
+
+Device cases run once with every payload 256-byte aligned and once at exactly
+the minimum alignment include/cda.h documents for the argument (the address is
+congruent to it modulo 256 and to nothing larger).  No case passes a pointer
+below that minimum to a kernel.
+
+Shapes are the smallest at which the stores differ: k = 1, 2, 4 (packed root
+strides 180, 360, 720), batches of 1, 3 and 17 squares, one GF(2^16) width for
+the codec.  The hash schedules of larger batches write the packed roots and
+data roots from other kernels; tests/test_hash_schedules.py runs every one of
+them on guarded root, data-root and status buffers.
+"""
+import ctypes as C
+import functools
+import os
+import re
+
+import numpy as np
+import pytest
+
+import guarded
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(os.path.dirname(HERE), "celestia-app_amd", "csrc")
+
+U8P, U32P, I32P, U64P = (C.POINTER(t) for t in (C.c_uint8, C.c_uint32, C.c_int32, C.c_uint64))
+OK, PUSH_ORDER, INVALID, BYZ, UNREP = 0, -3, -6, -9, -10
+SWEEP = "test_hash_schedules.py::test_sweep_batch_matches_oracle"
+
+# ---------------------------------------------------------------------------
+# Coverage table: every __global__ kernel of csrc/ is classified
+# ---------------------------------------------------------------------------
+# Kernels that store through a pointer an entry point received from its caller
+# -- directly (device entry points) or through a staging buffer whose bytes
+# are then copied to the caller's host buffer -- with the guarded case that
+# reaches the store.
+CALLER_OUTPUT = {
+    # nmt.hip
+    "row_order_kernel": "test_split_rows",                      # d_err
+    "leaf_pair_kernel": "test_split_cols_and_combine",          # d_err of cda_split_cols
+    "level_kernel": "test_split_cols_and_combine",              # slot outputs; packed roots: SWEEP
+    "subtree_kernel": SWEEP,                                    # packed roots of whole-tree subtree launches
+    "tree_top_kernel": "test_extend_dah_device",                # packed roots
+    "data_root_kernel": "test_split_cols_and_combine",          # d_data_root
+    "data_root_digest_kernel": "test_extend_dah_device",        # d_data_roots, d_status
+    "slots_to_roots_kernel": "test_split_cols_and_combine",     # d_row_roots, d_col_roots
+    # rs_gf8.hip / rs_gf16.hip / repair.hip
+    "rs8_job_kernel": "test_extend_dah_device",                 # d_eds, row / column blocks
+    "rs8_flat_kernel": "test_rs_encode_decode",                 # parity (staged)
+    "rs16_flat_kernel": "test_rs_encode_decode",
+    "decode_kernel": "test_rs_encode_decode",                   # GF(2^16) shards (staged)
+    "decode8_kernel": "test_repair_device",                     # d_eds in place
+    # engine.hip / comm.hip / square.hip / commit.hip
+    "pack_parity_kernel": "test_batch_ex_modes",
+    "group_rows_kernel": "test_split_rows",                     # d_send
+    "share_writer_kernel": "test_square_construct_device",      # d_ods
+    "commitment_kernel": "test_resident_proofs_guarded",        # commitments of cda_square_commitment_proofs
+    "commitment_group_kernel": "test_blob_commitments_device",  # d_commitments
+    "commitment_fused_kernel": "test_blob_commitments_device",
+    # tree.hip
+    "gen_pack_roots_kernel": "test_nmt_axis_roots",
+    "gen_gather_nodes_kernel": "test_nmt_prove_range",
+    "gen_rfc_levels_kernel": "test_merkle_and_data_root",
+    # resident squares and verifiers (host outputs, staged)
+    "gather_kernel": "test_square_subtree_root",
+    "sample_kernel": "test_sample_proofs",
+    "share_proofs_kernel": "test_resident_proofs_guarded",
+    "befp_build_kernel": "test_befp_build",
+    "befp_compare_kernel": "test_verifier_outputs_guarded",     # verdict, rebuilt_roots
+    "vp_verdict_kernel": "test_verifier_outputs_guarded",
+    "vn_verdict_kernel": "test_verifier_outputs_guarded",
+    "vc_verdict_kernel": "test_verifier_outputs_guarded",
+}
+# Caller-pointer stores that no guarded case reaches, because the kernel runs
+# only above the widths this module and the guarded sweep cover (the sweep
+# leaves the EDS unguarded from k = 128 up, to keep memory down).  Each names
+# the oracle-pinned test that runs it.
+WIDE_ONLY = {
+    "leaf_kernel": ("d_err of cda_split_cols above 32768 cells (k >= 128)",
+                    "test_gpu_parity.py::test_split_square_loopback_on_gpu"),
+    "rs8_bs_kernel": ("d_eds at k = 128", SWEEP),
+    "rs8_bs_half_kernel": ("d_eds at k = 128", SWEEP),
+    "rs16_bs_kernel": ("d_eds at k = 256, 512", SWEEP),
+    "rs16_lds_kernel": ("d_eds at k = 1024, a width no test runs", None),
+}
+# Kernels whose every store goes to the context's or the resident square's own
+# memory (slots, digests, flags, plans, error words that the host decodes).
+SCRATCH_ONLY = {
+    "rfc_leaf_kernel", "status_kernel", "errloc_kernel", "mark_kernel", "parity_compare_kernel", "order_kernel",
+    "verdict_kernel", "blob_leaf_kernel", "leaf_roots_kernel", "subtree_level_kernel", "slot_digest_kernel",
+    "gen_leaf_kernel", "gen_level_kernel", "gen_rfc_leaf_kernel", "rfc_levels_kernel", "namespace_search_kernel",
+    "befp_scatter_kernel", "vp_leaf_kernel", "vp_fold_kernel", "vp_row_kernel", "vn_complete_kernel", "vc_fold_kernel",
+}
+
+
+def _kernels():
+    names = set()
+    for f in sorted(os.listdir(CSRC)):
+        if f.endswith(".hip"):
+            with open(os.path.join(CSRC, f)) as fh:
+                src = fh.read()
+            for m in re.finditer(r"__global__\b[^;{]*?\bvoid\s+(\w+)\s*\(", src, re.S):
+                names.add(m.group(1))
+    return names
+
+
+def _test_exists(where):
+    path, name = where.split("::") if "::" in where else (os.path.basename(__file__), where)
+    with open(os.path.join(HERE, path)) as f:
+        return re.search(rf"^def {name}\(", f.read(), re.M) is not None
+
+
+def test_every_kernel_is_classified():
+    """A new __global__ kernel must be put into one of the three lists: with
+    its footprint case when it stores through a caller's pointer."""
+    found = _kernels()
+    assert len(found) >= 50, sorted(found)
+    lists = (set(CALLER_OUTPUT), set(WIDE_ONLY), SCRATCH_ONLY)
+    for a in range(3):
+        for b in range(a + 1, 3):
+            assert not lists[a] & lists[b], sorted(lists[a] & lists[b])
+    known = lists[0] | lists[1] | lists[2]
+    assert not found - known, f"unclassified kernels (add a footprint case or list them): {sorted(found - known)}"
+    assert not known - found, f"listed kernels that no longer exist: {sorted(known - found)}"
+    for kernel, case in CALLER_OUTPUT.items():
+        assert _test_exists(case), (kernel, case)
+    for kernel, (_, case) in WIDE_ONLY.items():
+        assert case is None or _test_exists(case), (kernel, case)
+
+
+# ---------------------------------------------------------------------------
+# Alignment contract: the table of include/cda.h
+# ---------------------------------------------------------------------------
+# The minimum alignment of a device pointer is the widest access a kernel
+# makes straight through it.  The device cases below place every payload at
+# exactly this value once; no case passes a pointer below it to a kernel.
+ALIGN = {"shares": 16, "slots": 16, "roots": 2, "digests": 4, "words": 4, "written_ods": 8, "bytes": 4}
+
+# Every entry point that takes device pointers, with the kind of each.
+DEVICE_POINTERS = {
+    "cda_extend_dah_device": [("d_ods", "shares"), ("d_eds", "shares"), ("d_row_roots", "roots"),
+                              ("d_col_roots", "roots"), ("d_data_roots", "digests"), ("d_status", "words")],
+    "cda_extend_dah_inplace_device": [("d_eds", "shares"), ("d_row_roots", "roots"), ("d_col_roots", "roots"),
+                                      ("d_data_roots", "digests"), ("d_status", "words")],
+    "cda_split_rows": [("d_ods_rows", "shares"), ("d_row_block", "shares"), ("d_err", "words")],
+    "cda_split_cols": [("d_col_block", "shares"), ("d_col_root_slots", "slots"), ("d_row_subtree_slots", "slots"),
+                       ("d_err", "words")],
+    "cda_split_combine": [("d_row_subtree_slots", "slots"), ("d_col_root_slots", "slots"), ("d_row_roots", "roots"),
+                          ("d_col_roots", "roots"), ("d_data_root", "digests")],
+    "cda_split_rows_send": [("d_ods_rows", "shares"), ("d_send", "shares"), ("d_err", "words")],
+    "cda_extend_dah_split": [("d_ods_rows", "shares"), ("d_col_block", "shares"), ("d_row_roots", "roots"),
+                             ("d_col_roots", "roots"), ("d_data_root", "digests"), ("d_err", "words")],
+    "cda_square_construct_device": [("d_txs", "bytes"), ("d_ods", "written_ods")],
+    "cda_blob_commitments_device": [("d_data", "bytes"), ("d_commitments", "digests")],
+    "cda_repair_device": [("d_eds", "shares")],
+    "cda_repair_batch_device": [("d_eds", "shares")],
+    "cda_befp_build_device": [("d_eds", "shares")],
+}
+
+
+def test_header_states_the_alignment_of_every_device_pointer():
+    """Every void* / device argument of include/cda.h is in DEVICE_POINTERS, and
+    the header's comments give each one the alignment of its kind."""
+    with open(os.path.join(os.path.dirname(HERE), "include", "cda.h")) as f:
+        header = f.read()
+    code = re.sub(r"/\*.*?\*/", " ", header, flags=re.S)
+    declared = {}
+    for fn, args in re.findall(r"\bint\s+(cda_\w+)\s*\(([^)]*)\)\s*;", code):
+        names = re.findall(r"\b(d_\w+)\b", args)
+        if names:
+            declared[fn] = names
+    assert {fn: [a for a, _ in v] for fn, v in DEVICE_POINTERS.items()} == declared
+    flat = " ".join(header.replace("*", " ").split())
+    for fn, args in DEVICE_POINTERS.items():
+        for arg, kind in args:
+            assert re.search(rf"\b{arg}\b[^.;]*? {ALIGN[kind]}\b", flat), (fn, arg, ALIGN[kind])
+
+
+# ---------------------------------------------------------------------------
+# GPU cases: helpers
+# ---------------------------------------------------------------------------
+MODES = ["aligned256", "minimum"]
+
+
+def _al(kind, mode):
+    return ALIGN[kind] if mode == "minimum" else 256
+
+
+def _dev(size, stride, kind, mode, name):
+    g = guarded.alloc(size, stride=stride, align=_al(kind, mode), backend="torch", name=name)
+    if mode == "minimum":
+        assert g.ptr % 256 == ALIGN[kind]
+    return g
+
+
+def _dev_in(data, stride, kind, mode, name):
+    return guarded.from_data(data, stride=stride, align=_al(kind, mode), backend="torch", name=name)
+
+
+def _host(size, stride=0, name="buffer", align=64):
+    return guarded.alloc(size, stride=stride, align=align, backend="numpy", name=name)
+
+
+def _host_in(data, stride=0, name="input"):
+    return guarded.from_data(data, stride=stride, align=64, backend="numpy", name=name)
+
+
+def _p(g, t=U8P):
+    return C.cast(g.ptr, t)
+
+
+def _sync():
+    import torch
+    torch.cuda.synchronize()
+
+
+def _stream():
+    import torch
+    return torch.cuda.current_stream(torch.device("cuda", 0)).cuda_stream
+
+
+def _first_violation(q0):
+    """Brute-force nmt push-order check of one Q0 (k, k, 512): the smallest
+    (axis, index, position), rows before columns, or None."""
+    k = q0.shape[0]
+    ns = [[q0[r, c, :29].tobytes() for c in range(k)] for r in range(k)]
+    bad = [(0, r, c) for r in range(k) for c in range(1, k) if ns[r][c] < ns[r][c - 1]]
+    bad += [(1, c, r) for c in range(k) for r in range(1, k) if ns[r][c] < ns[r - 1][c]]
+    return min(bad) if bad else None
+
+
+@functools.lru_cache(maxsize=None)
+def _square(k, seed, swapped=False):
+    """(ods, eds, rows, cols, root, first violation) of one square, read-only;
+    swapped: two different neighbouring Q0 namespaces of a row exchanged (the
+    roots are then the blind oracle's, as the header documents)."""
+    import coracle
+    ods = coracle.random_square(k, seed).reshape(k, k, 512).copy()
+    if swapped:
+        pairs = [(r, c) for r in range(k) for c in range(k - 1) if ods[r, c, :29].tobytes() != ods[r, c + 1, :29].tobytes()]
+        if pairs:
+            r, c = pairs[-1]
+            ods[r, c, :29], ods[r, c + 1, :29] = ods[r, c + 1, :29].copy(), ods[r, c, :29].copy()
+    eds, rows, cols, root = coracle.blind_extend_dah(ods.reshape(-1, 512))
+    out = (ods.reshape(k * k, 512), eds, rows, cols, np.frombuffer(root, dtype=np.uint8), _first_violation(ods))
+    for a in out[:5]:
+        a.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _batch(k, n):
+    """n squares of width k, the second one out of namespace order when there
+    is one: stacked (ods, eds, rows, cols, roots, status)."""
+    sq = [_square(k, 40 + i, swapped=(i == 1)) for i in range(n)]
+    stack = lambda j: np.stack([s[j] for s in sq])   # noqa: E731
+    status = np.array([PUSH_ORDER if s[5] is not None else OK for s in sq], dtype=np.int32)
+    return stack(0), stack(1), stack(2), stack(3), stack(4), status
+
+
+KN = [(k, n) for k in (1, 2, 4) for n in (1, 3, 17)]
+
+
+# ---------------------------------------------------------------------------
+# cda_extend_dah_device / cda_extend_dah_inplace_device
+# ---------------------------------------------------------------------------
+def _extend_outputs(k, n, mode):
+    W = 2 * k
+    return (_dev(n * W * W * 512, W * W * 512, "shares", mode, "d_eds"),
+            _dev(n * W * 90, W * 90, "roots", mode, "d_row_roots"),
+            _dev(n * W * 90, W * 90, "roots", mode, "d_col_roots"),
+            _dev(n * 32, 32, "digests", mode, "d_data_roots"),
+            _dev(n * 4, 4, "words", mode, "d_status"))
+
+
+def _check_extend(outs, want, with_status):
+    eds, rows, cols, roots, status = outs
+    e_eds, e_rows, e_cols, e_roots, e_status = want
+    eds.assert_written(e_eds)
+    rows.assert_written(e_rows)
+    cols.assert_written(e_cols)
+    roots.assert_written(e_roots)
+    if with_status:
+        status.assert_written(e_status)
+    else:
+        status.assert_untouched()
+    for g in outs:
+        g.assert_guards()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("k,n", KN)
+def test_extend_dah_device(ctx, k, n, mode):
+    """d_eds, both root arrays, the data roots and the status words hold the
+    oracle's bytes and nothing around them changes; d_ods is read only; with
+    d_status NULL no status word is written anywhere."""
+    ods, *want = _batch(k, n)
+    if n > 1 and k >= 2:
+        assert want[4][1] == PUSH_ORDER
+    d_ods = _dev_in(ods, k * k * 512, "shares", mode, "d_ods")
+    outs = _extend_outputs(k, n, mode)
+    for with_status in (True, False):
+        ctx.extend_dah_device(d_ods.ptr, k, n, *[g.ptr for g in outs[:4]], outs[4].ptr if with_status else None,
+                              _stream())
+        _sync()
+        _check_extend(outs, want, with_status)
+        d_ods.assert_unchanged()
+        for g in outs:
+            g.refill()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("k,n", KN)
+def test_extend_dah_inplace_device(ctx, k, n, mode):
+    """Q0 of d_eds is the caller's and stays as it is; the three parity
+    quadrants are written (a cell left as pattern is reported as not written)."""
+    import torch
+    ods, *want = _batch(k, n)
+    W = 2 * k
+    outs = _extend_outputs(k, n, mode)
+    q0 = torch.from_numpy(ods.reshape(n, k, k, 512).copy()).to("cuda")
+    outs[0].payload().view(n, W, W, 512)[:, :k, :k] = q0
+    ctx.extend_dah_inplace_device(k, n, *[g.ptr for g in outs], _stream())
+    _sync()
+    assert torch.equal(outs[0].payload().view(n, W, W, 512)[:, :k, :k], q0)
+    _check_extend(outs, want, True)
+
+
+# ---------------------------------------------------------------------------
+# cda_split_rows / cda_split_rows_send / cda_split_cols / cda_split_combine
+# ---------------------------------------------------------------------------
+SPLITS = [(1, 1), (2, 1), (4, 1), (2, 2), (4, 2), (4, 4), (8, 8)]   # (k, parts): world 1, and the loopback test's parts
+
+
+def _err_word(v):
+    return None if v is None else (v[0] << 24) | (v[1] << 12) | v[2]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("k,parts", SPLITS)
+def test_split_rows(ctx, k, parts, mode):
+    _split_rows(ctx, k, parts, mode, False)
+
+
+@pytest.mark.gpu
+def test_split_rows_reports_a_violation_in_one_word(ctx):
+    assert _square(4, 9, True)[5] is not None
+    _split_rows(ctx, 4, 2, "minimum", True)
+
+
+def _split_rows(ctx, k, parts, mode, swapped):
+    """The row block, the same block in the send layout, and exactly one
+    push-order word per call."""
+    ods, eds, _, _, _, _ = _square(k, 9, swapped)
+    W, R, Cc = 2 * k, k // parts, 2 * k // parts
+    eds = eds.reshape(W, W, 512)
+    for g in range(parts):
+        rows_in = _dev_in(ods.reshape(k, k, 512)[g * R:(g + 1) * R], k * 512, "shares", mode, "d_ods_rows")
+        want_blk = eds[g * R:(g + 1) * R]
+        row_viol = [(0, r, c) for r in range(g * R, (g + 1) * R) for c in range(1, k)
+                    if ods.reshape(k, k, 512)[r, c, :29].tobytes() < ods.reshape(k, k, 512)[r, c - 1, :29].tobytes()]
+        want_err = np.array([_err_word(min(row_viol)) if row_viol else 0xFFFFFFFF], dtype=np.uint32)
+        blk = _dev(R * W * 512, W * 512, "shares", mode, "d_row_block")
+        err = _dev_in(np.array([0xFFFFFFFF], dtype=np.uint32), 4, "words", mode, "d_err")
+        ctx.split_rows(rows_in.ptr, k, R, g * R, blk.ptr, err.ptr, _stream())
+        _sync()
+        blk.assert_written(want_blk)
+        err.assert_written(want_err)
+        blk.assert_guards()
+        err.assert_guards()
+        rows_in.assert_unchanged()
+        send = _dev(parts * R * Cc * 512, R * Cc * 512, "shares", mode, "d_send")
+        err2 = _dev_in(np.array([0xFFFFFFFF], dtype=np.uint32), 4, "words", mode, "d_err")
+        ctx.split_rows_send(rows_in.ptr, k, R, g * R, parts, send.ptr, err2.ptr, _stream())
+        _sync()
+        send.assert_written(np.ascontiguousarray(want_blk.reshape(R, parts, Cc, 512).transpose(1, 0, 2, 3)))
+        err2.assert_written(want_err)
+        send.assert_guards()
+        err2.assert_guards()
+        rows_in.assert_unchanged()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("k,parts", SPLITS)
+def test_split_cols_and_combine(ctx, k, parts, mode):
+    """Column blocks (rows 0..k-1 the caller's, rows k..2k-1 written), the
+    column-root and row-subtree slots, one push-order word; then the combine
+    on the gathered slots: packed roots and the data root, slots unchanged."""
+    import torch
+    from split_cpu_ops import CpuSplitOps
+    ods, eds, e_rows, e_cols, e_root, _ = _square(k, 9)
+    W, Cc = 2 * k, 2 * k // parts
+    eds = eds.reshape(W, W, 512)
+    cpu = CpuSplitOps()
+    subs, colslots = [], []
+    for h in range(parts):
+        want_block = np.ascontiguousarray(eds[:, h * Cc:(h + 1) * Cc])
+        top = want_block.copy()
+        top[k:] = 0
+        cs, rs = cpu.cols(torch.from_numpy(top.copy()), k, h * Cc, cpu.new_err())
+        block = _dev(W * Cc * 512, Cc * 512, "shares", mode, "d_col_block")
+        given = torch.from_numpy(want_block[:k].copy()).to("cuda")
+        block.payload().view(W, Cc, 512)[:k] = given
+        d_cs = _dev(Cc * 96, 96, "slots", mode, "d_col_root_slots")
+        d_rs = _dev(W * 96, 96, "slots", mode, "d_row_subtree_slots")
+        err = _dev_in(np.array([0xFFFFFFFF], dtype=np.uint32), 4, "words", mode, "d_err")
+        ctx.split_cols(block.ptr, k, Cc, h * Cc, d_cs.ptr, d_rs.ptr, err.ptr, _stream())
+        _sync()
+        block.assert_written(want_block)
+        d_cs.assert_written(cs.numpy())
+        d_rs.assert_written(rs.numpy())
+        err.assert_written(np.array([0xFFFFFFFF], dtype=np.uint32))
+        for g in (block, d_cs, d_rs, err):
+            g.assert_guards()
+        assert np.array_equal(cs.numpy()[:, :90], e_cols[h * Cc:(h + 1) * Cc])
+        subs.append(rs.numpy())
+        colslots.append(cs.numpy())
+    sub_all = _dev_in(np.stack(subs), W * 96, "slots", mode, "d_row_subtree_slots")
+    col_all = _dev_in(np.concatenate(colslots), 96, "slots", mode, "d_col_root_slots")
+    rows = _dev(W * 90, W * 90, "roots", mode, "d_row_roots")
+    cols = _dev(W * 90, W * 90, "roots", mode, "d_col_roots")
+    root = _dev(32, 32, "digests", mode, "d_data_root")
+    ctx.split_combine(sub_all.ptr, parts, k, col_all.ptr, rows.ptr, cols.ptr, root.ptr, _stream())
+    _sync()
+    rows.assert_written(e_rows)
+    cols.assert_written(e_cols)
+    root.assert_written(e_root)
+    for g in (rows, cols, root):
+        g.assert_guards()
+    sub_all.assert_unchanged()
+    col_all.assert_unchanged()
+
+
+# ---------------------------------------------------------------------------
+# cda_square_construct_device / cda_blob_commitments_device: outputs, and the
+# documented over-read of up to 16 bytes past d_txs / d_data
+# ---------------------------------------------------------------------------
+FIRST, CONT = 478, 482                       # blob bytes in a first / a continuation share
+EDGE = (0, 1, 15, 16, 17)                    # bytes between the blob's end and the share boundary
+EDGE_LENGTHS = [FIRST - d for d in EDGE] + [FIRST + 2 * CONT - d for d in EDGE]
+
+
+def _with_tail(data, over, beyond):
+    """data | 16 readable bytes of value `over` | 48 bytes `beyond`: what a
+    caller's arena may hold after the buffer."""
+    return np.concatenate([np.frombuffer(bytes(data), dtype=np.uint8), np.full(16, over, dtype=np.uint8),
+                           np.frombuffer(beyond, dtype=np.uint8)])
+
+
+TAILS = [(0x00, bytes(range(1, 49))), (0xFF, bytes(255 - i for i in range(48)))]
+
+
+def _edge_block(last_len, seed):
+    """Two normal txs and three single-blob txs; the last blob has last_len bytes."""
+    from celestia_da import blobfactory
+    rng = np.random.default_rng(seed)
+    txs = [blobfactory.normal_tx(rng, 90), blobfactory.normal_tx(rng, 301)]
+    for size in (700, 2 * CONT + 5, last_len):
+        ns = blobfactory.random_blob_namespace_id(rng)
+        txs.append(blobfactory.blob_tx(rng.integers(0, 256, 40 + int(rng.integers(0, 4)), dtype=np.uint8).tobytes(),
+                                       [(ns, rng.integers(0, 256, size, dtype=np.uint8).tobytes())]))
+    return txs
+
+
+def _construct_cases():
+    from test_square import CASES, case_txs
+    yield "seed1", lambda: case_txs(CASES[0]), CASES[0][-1]
+    yield "seed6", lambda: case_txs(CASES[5]), CASES[5][-1]
+    for i, n in enumerate(EDGE_LENGTHS):
+        yield f"last{n}", functools.partial(_edge_block, n, 100 + i), 16
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name,make,max_ss", list(_construct_cases()), ids=[c[0] for c in _construct_cases()])
+def test_square_construct_device(ctx, name, make, max_ss, mode):
+    """square_size^2 * 512 bytes of d_ods equal go-square's shares and the rest
+    of ods_capacity stays pattern; the result is the same whether the 16
+    readable bytes after d_txs are 0x00 or 0xFF and whatever lies beyond them."""
+    import square as osq
+    from celestia_da import square as gsq
+    txs = make()
+    sh, ss, _, _ = osq.builder(txs, max_ss, 64, "build")
+    want = np.frombuffer(b"".join(sh), dtype=np.uint8)
+    assert ss <= 64 and want.size == ss * ss * 512
+    buf, off = gsq._flatten(txs)
+    n_bytes = int(off[-1])
+    cap = ss * ss * 512 + 3 * 512 + 8
+    for over, beyond in TAILS:
+        d_txs = _dev_in(_with_tail(buf[:n_bytes], over, beyond), 0, "bytes", mode, "d_txs")
+        d_ods = _dev(cap, ss * 512, "written_ods", mode, "d_ods")
+        kk = C.c_uint32()
+        ctx.check(ctx.lib.cda_square_construct_device(ctx.h, gsq.ptr(buf), gsq._u64p(off), len(txs), d_txs.ptr, max_ss,
+                                                      64, 1, d_ods.ptr, cap, C.byref(kk), None, None, _stream()))
+        _sync()
+        assert kk.value == ss
+        written = np.zeros(cap, bool)
+        written[:want.size] = True
+        d_ods.assert_written(np.concatenate([want, np.zeros(cap - want.size, np.uint8)]), written)
+        d_ods.assert_guards()
+        d_txs.assert_unchanged()
+
+
+def _blobs(sizes, seed):
+    from test_commitments import random_blobs
+    return random_blobs(seed, sizes)
+
+
+COMMIT_CASES = [("sizes", None)] + [(f"last{n}", n) for n in EDGE_LENGTHS]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("name,last", COMMIT_CASES, ids=[c[0] for c in COMMIT_CASES])
+def test_blob_commitments_device(ctx, name, last, mode):
+    """n * 32 bytes of commitments equal the oracle's, whether the 16 readable
+    bytes after d_data are 0x00 or 0xFF and whatever lies beyond them.  The
+    last blob ends where d_data ends, 0 .. 17 bytes before a share boundary."""
+    import inclusion as oinc
+    from test_commitments import SIZES
+    sizes = list(SIZES) if last is None else [1, 479, 30_000, last]
+    blobs = _blobs(sizes, 13)
+    n = len(blobs)
+    want = np.frombuffer(b"".join(oinc.create_commitment(b.namespace, b.data) for b in blobs), dtype=np.uint8)
+    ns = _host_in(np.frombuffer(b"".join(b.namespace for b in blobs), dtype=np.uint8), 29, "namespaces")
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b.data) for b in blobs])
+    d_off = _host_in(off, 8, "data_off")
+    data = b"".join(b.data for b in blobs)
+    for over, beyond in TAILS:
+        d_data = _dev_in(_with_tail(data, over, beyond), 0, "bytes", mode, "d_data")
+        d_out = _dev(n * 32, 32, "digests", mode, "d_commitments")
+        ctx.check(ctx.lib.cda_blob_commitments_device(ctx.h, _p(ns), _p(d_off, U64P), None, n, 64, d_data.ptr,
+                                                      d_out.ptr, _stream()))
+        _sync()
+        d_out.assert_written(want)
+        d_out.assert_guards()
+        d_data.assert_unchanged()
+        ns.assert_unchanged()
+        d_off.assert_unchanged()
+
+
+@pytest.mark.gpu
+def test_blob_commitments_host(ctx):
+    import inclusion as oinc
+    blobs = _blobs([1, 2, 477, 478, 479, 960, 961, 4000, 0, 478 + 482 * 63 + 1], 5)
+    n = len(blobs)
+    want = np.frombuffer(b"".join(oinc.create_commitment(b.namespace, b.data) for b in blobs), dtype=np.uint8)
+    ns = _host_in(np.frombuffer(b"".join(b.namespace for b in blobs), dtype=np.uint8), 29, "namespaces")
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(b.data) for b in blobs])
+    d_off = _host_in(off, 8, "data_off")
+    data = _host_in(np.frombuffer(b"".join(b.data for b in blobs), dtype=np.uint8), 0, "data")
+    out = _host(n * 32, 32, "commitments")
+    ctx.check(ctx.lib.cda_blob_commitments(ctx.h, _p(ns), _p(data), _p(d_off, U64P), None, n, 64, _p(out)))
+    out.assert_written(want)
+    out.assert_guards()
+    for g in (ns, d_off, data):
+        g.assert_unchanged()
+
+
+# ---------------------------------------------------------------------------
+# Repair: cda_repair_device, cda_repair_batch_device, cda_repair, cda_repair_batch
+# ---------------------------------------------------------------------------
+def _roots_bytes(roots):
+    return np.frombuffer(b"".join(bytes(r) for r in roots), dtype=np.uint8)
+
+
+def _repair_cases(k):
+    """(eds, present, rows, cols, outcome) with every outcome the width has:
+    ok, unrepairable, and from k = 2 byzantine; outcomes are the oracle's."""
+    from test_repair import run_oracle, small_eds
+    W = 2 * k
+    eds, rows, cols = small_eds(k, 12)
+    rng = np.random.default_rng(500 + k)
+    cases = []
+    q0 = np.ones((W, W), bool)
+    q0[:k, :k] = False
+    none = np.zeros((W, W), bool)
+    none[: max(1, k - 1), : max(1, k - 1)] = True
+    for p in (q0, rng.random((W, W)) < 0.6, none):
+        cases.append((eds, p, rows, cols))
+    if k >= 2:
+        from test_repair_batch import decode_exposed
+        cases.append(decode_exposed(k))
+    out = []
+    for e, p, r, c in cases:
+        out.append((e, np.asarray(p, bool), r, c, run_oracle(e, np.asarray(p, bool), r, c)[0]))
+    kinds = {o[4] if isinstance(o[4], str) else "byz" for o in out}
+    assert {"ok"} <= kinds and (k == 1 or {"unrep", "byz"} <= kinds), kinds
+    return out
+
+
+def _held(eds, present):
+    return np.where(present[..., None], eds, 0).astype(np.uint8)
+
+
+def _code(outcome):
+    return BYZ if isinstance(outcome, tuple) else {"ok": OK, "unrep": UNREP, "badroot": INVALID}[outcome]
+
+
+def _check_repaired(got, eds, present, outcome, name):
+    """Cells present in the input unchanged whatever the outcome; the whole
+    square equal to the original when repaired."""
+    assert np.array_equal(got[present], eds[present]), f"{name}: a cell present in the input changed ({outcome})"
+    if outcome == "ok":
+        assert np.array_equal(got, eds), f"{name}: repaired square differs from the original"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("k", [1, 2, 4])
+def test_repair_device(ctx, k, mode):
+    W = 2 * k
+    for i, (eds, present, rows, cols, outcome) in enumerate(_repair_cases(k)):
+        d = _dev_in(_held(eds, present), W * 512, "shares", mode, "d_eds")
+        p = _host_in(present.astype(np.uint8), W, "present")
+        rb, cb = _host_in(_roots_bytes(rows), 90, "row_roots"), _host_in(_roots_bytes(cols), 90, "col_roots")
+        ax, ix = _host(4, name="byz_axis"), _host(4, name="byz_index")
+        rc = ctx.lib.cda_repair_device(ctx.h, d.ptr, _p(p), W, _p(rb), _p(cb), _p(ax, I32P), _p(ix, U32P))
+        assert rc == _code(outcome), (i, rc, outcome)
+        _check_repaired(d.payload_host().reshape(W, W, 512), eds, present, outcome, f"case {i}")
+        d.assert_guards()
+        got_ax = int(ax.payload_host().view(np.int32)[0])
+        if isinstance(outcome, tuple):
+            assert (got_ax, int(ix.payload_host().view(np.uint32)[0])) == outcome[1:]
+        else:
+            assert got_ax == -1
+        for g in (ax, ix):
+            g.assert_guards()
+        for g in (p, rb, cb):
+            g.assert_unchanged()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [1, 2, 4])
+def test_repair_host(ctx, k):
+    W = 2 * k
+    for i, (eds, present, rows, cols, outcome) in enumerate(_repair_cases(k)):
+        e = _host_in(_held(eds, present), W * 512, "eds")
+        p = _host_in(present.astype(np.uint8), W, "present")
+        rb, cb = _host_in(_roots_bytes(rows), 90, "row_roots"), _host_in(_roots_bytes(cols), 90, "col_roots")
+        ax, ix = _host(4, name="byz_axis"), _host(4, name="byz_index")
+        rc = ctx.lib.cda_repair(ctx.h, _p(e), _p(p), W, _p(rb), _p(cb), _p(ax, I32P), _p(ix, U32P))
+        assert rc == _code(outcome), (i, rc, outcome)
+        _check_repaired(e.payload_host().reshape(W, W, 512), eds, present, outcome, f"case {i}")
+        for g in (e, ax, ix):
+            g.assert_guards()
+        for g in (p, rb, cb):
+            g.assert_unchanged()
+
+
+@functools.lru_cache(maxsize=None)
+def _repair_batch(n):
+    """test_one_more_than_a_chunk's batch shape: n squares of width 4 from four
+    DAHs, random presence, a bad root input in the first and the last square
+    of the range (so in each chunk when n is one more than a chunk)."""
+    from test_repair import run_oracle, small_eds
+    k, W = 2, 4
+    squares = [small_eds(k, 70 + s) for s in range(4)]
+    rng = np.random.default_rng(71)
+    cases = []
+    for i in range(n):
+        e, r, c = squares[i % 4]
+        cases.append((e, rng.random((W, W)) < (0.35 + 0.1 * (i % 6)), r, c))
+    for i in {min(3, n - 1), n - 1}:
+        e, r, c = squares[i % 4]
+        bad = e.copy()
+        bad[0, 1, 300] ^= 1
+        cases[i] = (bad, np.ones((W, W), bool), r, c)
+    outcomes = [run_oracle(e, p, r, c)[0] for e, p, r, c in cases]
+    return cases, outcomes
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("where", ["device", "host"])
+@pytest.mark.parametrize("n", [1, 3, 17, 257])
+def test_repair_batch(ctx, n, where):
+    """n = 257 is one more than a chunk of the batch (256 squares): the last
+    chunk's square must land in its own slice and nowhere after it."""
+    from celestia_da import rsmt2d
+    k, W = 2, 4
+    assert rsmt2d.repair_batch_chunk(W) == 256
+    cases, outcomes = _repair_batch(n)
+    held = np.stack([_held(e, p) for e, p, _, _ in cases])
+    present = np.stack([p for _, p, _, _ in cases]).astype(np.uint8)
+    p = _host_in(present, W * W, "present")
+    rb = _host_in(np.stack([_roots_bytes(r) for _, _, r, _ in cases]), W * 90, "row_roots")
+    cb = _host_in(np.stack([_roots_bytes(c) for _, _, _, c in cases]), W * 90, "col_roots")
+    status, axis, index = _host(4 * n, 4, "status"), _host(4 * n, 4, "byz_axis"), _host(4 * n, 4, "byz_index")
+    tail = (_p(p), W, n, _p(rb), _p(cb), _p(status, I32P), _p(axis, I32P), _p(index, U32P))
+    if where == "device":
+        d = _dev_in(held, W * W * 512, "shares", "minimum", "d_eds")
+        rc = ctx.lib.cda_repair_batch_device(ctx.h, d.ptr, *tail)
+    else:
+        d = _host_in(held, W * W * 512, "eds")
+        rc = ctx.lib.cda_repair_batch(ctx.h, _p(d), *tail)
+    assert rc == OK
+    got = d.payload_host().reshape(n, W, W, 512)
+    st = status.payload_host().view(np.int32)
+    assert st.tolist() == [_code(o) for o in outcomes]
+    for i, (e, pm, _, _) in enumerate(cases):
+        _check_repaired(got[i], e, np.asarray(pm, bool), outcomes[i], f"square {i}")
+    want_axis = np.array([o[1] if isinstance(o, tuple) else -1 for o in outcomes], dtype=np.int32)
+    axis.assert_written(want_axis)
+    for g in (d, status, axis, index):
+        g.assert_guards()
+    for g in (p, rb, cb):
+        g.assert_unchanged()
+
+
+# ---------------------------------------------------------------------------
+# cda_befp_build / cda_befp_build_device
+# ---------------------------------------------------------------------------
+@pytest.mark.gpu
+@pytest.mark.parametrize("where", ["device-aligned256", "device-minimum", "host"])
+def test_befp_build(ctx, where):
+    """The square with holes of test_builder_skips_cells_whose_orthogonal_
+    vector_has_a_hole: *n_out < w, and everything past *n_out entries of
+    positions, shares and nmt_nodes stays pattern; the EDS is read only."""
+    import befp_ref as ref
+    k, W, D = 4, 8, 3
+    sq = ref.honest_square(k)
+    rows, cols = _host_in(sq.rows_array(), 90, "row_roots"), _host_in(sq.cols_array(), 90, "col_roots")
+    for axis, index, holes in ((ref.ROW, 1, ((0, 1), (5, 4), (7, 6))), (ref.COL, 6, ((0, 1), (3, 0), (7, 7)))):
+        eds = sq.eds.copy()
+        for r, c in holes:
+            eds[r, c] = 0
+        want = ref.build(eds, sq.rows, sq.cols, axis, index)
+        m = len(want.positions)
+        assert m == W - 3
+        n_out = _host(4, name="n_out")
+        pos, shares = _host(W * 4, 4, "positions"), _host(W * 512, 512, "shares")
+        nodes = _host(W * D * 90, D * 90, "nmt_nodes")
+        tail = (W, axis, index, _p(rows), _p(cols), _p(n_out, U32P), _p(pos, U32P), _p(shares), _p(nodes))
+        if where == "host":
+            e = _host_in(eds, W * 512, "eds")
+            ctx.check(ctx.lib.cda_befp_build(ctx.h, _p(e), *tail))
+        else:
+            e = _dev_in(eds, W * 512, "shares", where.split("-")[1], "d_eds")
+            ctx.check(ctx.lib.cda_befp_build_device(ctx.h, e.ptr, *tail))
+        n_out.assert_written(np.array([m], dtype=np.uint32))
+        for g, exp, width in ((pos, np.asarray(want.positions, dtype=np.uint32), 4),
+                              (shares, np.asarray(want.shares, dtype=np.uint8), 512),
+                              (nodes, np.asarray(want.nmt_nodes, dtype=np.uint8), D * 90)):
+            full = np.zeros(W * width, dtype=np.uint8)
+            full[:m * width] = np.ascontiguousarray(exp).reshape(-1).view(np.uint8)
+            mask = np.zeros(W * width, bool)
+            mask[:m * width] = True
+            g.assert_written(full, mask)
+            g.assert_guards()
+        n_out.assert_guards()
+        e.assert_unchanged()
+        rows.assert_unchanged()
+        cols.assert_unchanged()
+
+
+# ---------------------------------------------------------------------------
+# Host entry points
+# ---------------------------------------------------------------------------
+def _batch_ex(c, k, n, mode_id, ods_g, out_size, stride):
+    W = 2 * k
+    out = _host(out_size, stride, "eds")
+    rows, cols = _host(n * W * 90, W * 90, "row_roots"), _host(n * W * 90, W * 90, "col_roots")
+    roots, status = _host(n * 32, 32, "data_roots"), _host(n * 4, 4, "status")
+    rc = c.lib.cda_extend_dah_batch_ex(c.h, _p(ods_g), k, n, _p(out), mode_id, _p(rows), _p(cols), _p(roots),
+                                       _p(status, I32P))
+    return rc, out, rows, cols, roots, status
+
+
+def _check_batch_ex(k, n, mode, res, want):
+    rc, out, rows, cols, roots, status = res
+    e_eds, e_rows, e_cols, e_roots, e_status = want
+    W = 2 * k
+    assert rc == (PUSH_ORDER if (e_status != 0).any() else OK)
+    e = e_eds.reshape(n, W, W, 512)
+    if mode == "parity":     # exactly n*3*k*k*512 bytes: Q1 as k rows of k shares, then rows k..2k-1 whole
+        packed = np.concatenate([np.concatenate([e[i, :k, k:].reshape(-1), e[i, k:].reshape(-1)]) for i in range(n)])
+        assert packed.size == n * 3 * k * k * 512
+        out.assert_written(packed)
+    elif mode == "skip_q0":  # Q0 stays pattern
+        mask = np.ones((n, W, W, 512), bool)
+        mask[:, :k, :k] = False
+        out.assert_written(e, mask)
+    else:
+        out.assert_written(e)
+    rows.assert_written(e_rows)
+    cols.assert_written(e_cols)
+    roots.assert_written(e_roots)
+    status.assert_written(e_status)
+    for g in (out, rows, cols, roots, status):
+        g.assert_guards()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["full", "skip_q0", "parity"])
+@pytest.mark.parametrize("k,n", KN)
+def test_batch_ex_modes(ctx, k, n, mode):
+    from celestia_da import _lib
+    ods, *want = _batch(k, n)
+    W = 2 * k
+    ods_g = _host_in(ods, k * k * 512, "ods")
+    size = n * 3 * k * k * 512 if mode == "parity" else n * W * W * 512
+    mode_id = {"full": _lib.CDA_EDS_FULL, "skip_q0": _lib.CDA_EDS_SKIP_Q0, "parity": _lib.CDA_EDS_PARITY}[mode]
+    _check_batch_ex(k, n, mode, _batch_ex(ctx, k, n, mode_id, ods_g, size, size // n), want)
+    ods_g.assert_unchanged()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["full", "skip_q0", "parity"])
+def test_batch_ex_across_two_pipeline_chunks(ctx, mode):
+    """n = 5 with CDA_HOST_PIPE_CHUNK=2: two whole chunks and a ragged one."""
+    from celestia_da import _lib
+    from knobs import ctx_with
+    k, n = 4, 5
+    ods, *want = _batch(k, n)
+    W = 2 * k
+    ods_g = _host_in(ods, k * k * 512, "ods")
+    size = n * 3 * k * k * 512 if mode == "parity" else n * W * W * 512
+    mode_id = {"full": _lib.CDA_EDS_FULL, "skip_q0": _lib.CDA_EDS_SKIP_Q0, "parity": _lib.CDA_EDS_PARITY}[mode]
+    c = ctx_with({"CDA_HOST_PIPE_CHUNK": "2"}, test_build=False)
+    try:
+        res = _batch_ex(c, k, n, mode_id, ods_g, size, size // n)
+    finally:
+        c.close()
+    _check_batch_ex(k, n, mode, res, want)
+    ods_g.assert_unchanged()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_shards,shard_len,n_cw", [(1, 64, 3), (2, 64, 3), (4, 128, 17), (256, 64, 2)])
+def test_rs_encode_decode(ctx, n_shards, shard_len, n_cw):
+    """cda_rs_encode writes n_cw * n_shards * shard_len parity bytes;
+    cda_rs_decode rebuilds the missing shards in place and leaves the present
+    ones alone.  256 shards: GF(2^16)."""
+    import coracle
+    rng = np.random.default_rng(n_shards)
+    data = rng.integers(0, 256, (n_cw, n_shards, shard_len), dtype=np.uint8)
+    parity = np.stack([coracle.leopard_encode(d) for d in data])
+    d_in = _host_in(data, n_shards * shard_len, "data")
+    out = _host(parity.size, n_shards * shard_len, "parity")
+    ctx.check(ctx.lib.cda_rs_encode(ctx.h, _p(d_in), n_shards, shard_len, n_cw, _p(out)))
+    out.assert_written(parity)
+    out.assert_guards()
+    d_in.assert_unchanged()
+    cws = np.concatenate([data, parity], axis=1)
+    pres = np.ones((n_cw, 2 * n_shards), bool)
+    for i in range(n_cw):
+        pres[i, rng.choice(2 * n_shards, n_shards if i % 2 else max(1, n_shards // 2), replace=False)] = False
+    if n_cw >= 3:
+        pres[n_cw - 1] = True        # a complete codeword: nothing to write
+    held = np.where(pres[..., None], cws, 0).astype(np.uint8)
+    shards = _host_in(held, 2 * n_shards * shard_len, "shards")
+    p = _host_in(pres.astype(np.uint8), 2 * n_shards, "present")
+    ctx.check(ctx.lib.cda_rs_decode(ctx.h, _p(shards), _p(p), n_shards, shard_len, n_cw))
+    got = shards.payload_host().reshape(cws.shape)
+    assert np.array_equal(got, cws)
+    shards.assert_guards()
+    p.assert_unchanged()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [1, 2, 4])
+def test_sample_proofs(ctx, k):
+    """Every cell on both axes: the six arrays equal test_sampling's checker."""
+    from celestia_da import proof as gpr
+    from test_sampling import all_cells, checker
+    chk = checker(k)
+    coords = all_cells(k)
+    n, D = len(coords), (2 * k).bit_length() - 1
+    want = chk.arrays(coords)
+    rows = _host_in(coords[:, 0].astype(np.uint32), 4, "rows")
+    cols = _host_in(coords[:, 1].astype(np.uint32), 4, "cols")
+    axes = _host_in(coords[:, 2].astype(np.uint8), 1, "axes")
+    widths = (512, 29, D * 90, 90, 32, (D + 1) * 32)
+    names = ("shares", "namespaces", "nmt_nodes", "axis_roots", "leaf_hash", "aunts")
+    outs = [_host(n * w, w, nm, align=1 if w % 2 else 64) for w, nm in zip(widths, names)]
+    sq = gpr.ResidentSquare(chk.ods, ctx)
+    try:
+        ctx.check(ctx.lib.cda_square_sample_proofs(sq.h, _p(rows, U32P), _p(cols, U32P), _p(axes), n,
+                                                   *[_p(g) for g in outs]))
+    finally:
+        sq.close()
+    for g, exp in zip(outs, want):
+        g.assert_written(exp)
+        g.assert_guards()
+    for g in (rows, cols, axes):
+        g.assert_unchanged()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [1, 2, 4])
+def test_nmt_axis_roots(ctx, k):
+    """The rows of an EDS on the square kernels, and trees of 3 cells of 64
+    bytes on the generic ones (the second tree out of order: its status word
+    alone says so); n_trees * 90 root bytes and n_trees status words."""
+    import pyref
+    W = 2 * k
+    _, eds, e_rows, _, _, _ = _square(k, 3)
+    cells = _host_in(eds, W * 512, "cells")
+    axis = _host_in(np.arange(W, dtype=np.uint32), 4, "axis_index")
+    roots, status = _host(W * 90, 90, "roots"), _host(W * 4, 4, "status")
+    ctx.check(ctx.lib.cda_nmt_axis_roots(ctx.h, _p(cells), 512, W, W, k, _p(axis, U32P), _p(roots), _p(status, I32P)))
+    roots.assert_written(e_rows)
+    status.assert_written(np.zeros(W, dtype=np.int32))
+    for g in (roots, status):
+        g.assert_guards()
+    cells.assert_unchanged()
+    axis.assert_unchanged()
+    # generic kernels
+    rng = np.random.default_rng(k)
+    n_trees, n_cells, L = 3, 3, 64
+    raw = rng.integers(0, 256, (n_trees, n_cells, L), dtype=np.uint8)
+    raw[:, :, 0] = [10, 20, 30]              # namespaces ascending along every tree
+    raw[1, [0, 1]] = raw[1, [1, 0]]          # tree 1: first two cells out of order
+    ax = np.zeros(n_trees, dtype=np.uint32)
+    want = [pyref.axis_root([bytes(c) for c in raw[t]], 4, 0, blind=True) for t in range(n_trees)]
+    out_of_order = [bytes(raw[t, 1, :29]) < bytes(raw[t, 0, :29]) or bytes(raw[t, 2, :29]) < bytes(raw[t, 1, :29])
+                    for t in range(n_trees)]
+    assert out_of_order[1]
+    cells = _host_in(raw, n_cells * L, "cells")
+    axis = _host_in(ax, 4, "axis_index")
+    roots, status = _host(n_trees * 90, 90, "roots", align=2), _host(n_trees * 4, 4, "status")
+    rc = ctx.lib.cda_nmt_axis_roots(ctx.h, _p(cells), L, n_cells, n_trees, 4, _p(axis, U32P), _p(roots),
+                                    _p(status, I32P))
+    assert rc == PUSH_ORDER
+    roots.assert_written(np.frombuffer(b"".join(want), dtype=np.uint8))
+    status.assert_written(np.array([PUSH_ORDER if b else OK for b in out_of_order], dtype=np.int32))
+    for g in (roots, status):
+        g.assert_guards()
+    cells.assert_unchanged()
+    axis.assert_unchanged()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [1, 2, 4])
+def test_nmt_prove_range(ctx, k):
+    """nodes past *n_nodes stay pattern (the buffer holds the documented
+    maximum, 2 * ceil(log2 n_cells) nodes)."""
+    import proofs as opr
+    import pyref
+    W = 2 * k
+    _, eds, e_rows, _, _, _ = _square(k, 3)
+    row = np.ascontiguousarray(eds.reshape(W, W, 512)[0])
+    leaves = pyref.erasured_leaves([bytes(c) for c in row], k, 0)
+    cap = 2 * max(1, (W - 1).bit_length())
+    cells = _host_in(row, 512, "cells")
+    for start, end in {(0, 1), (W - 1, W), (0, W), (W // 2, W // 2 + 1)}:
+        want = b"".join(opr.nmt_range_proof(leaves, start, end))
+        nodes, n_nodes = _host(cap * 90, 90, "nodes", align=2), _host(4, name="n_nodes")
+        root = _host(90, name="root", align=2)
+        ctx.check(ctx.lib.cda_nmt_prove_range(ctx.h, _p(cells), 512, W, k, 0, start, end, _p(nodes), _p(n_nodes, U32P),
+                                              _p(root)))
+        n_nodes.assert_written(np.array([len(want) // 90], dtype=np.uint32))
+        full = np.zeros(cap * 90, dtype=np.uint8)
+        full[:len(want)] = np.frombuffer(want, dtype=np.uint8)
+        mask = np.zeros(cap * 90, bool)
+        mask[:len(want)] = True
+        nodes.assert_written(full, mask)
+        root.assert_written(e_rows[0])
+        for g in (nodes, n_nodes, root):
+            g.assert_guards()
+        cells.assert_unchanged()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [1, 2, 4])
+def test_merkle_and_data_root(ctx, k):
+    import pyref
+    W = 2 * k
+    _, _, e_rows, e_cols, e_root, _ = _square(k, 3)
+    rows, cols = _host_in(e_rows, 90, "row_roots"), _host_in(e_cols, 90, "col_roots")
+    out = _host(32, name="data_root", align=1)
+    ctx.check(ctx.lib.cda_data_root(ctx.h, _p(rows), _p(cols), W, _p(out)))
+    out.assert_written(e_root)
+    out.assert_guards()
+    rows.assert_unchanged()
+    cols.assert_unchanged()
+    # cda_merkle_root over items of odd lengths, an odd count
+    rng = np.random.default_rng(k)
+    items = [rng.integers(0, 256, int(n), dtype=np.uint8).tobytes() for n in (1, 90, 33, 0, 7)[: 2 * k + 1]]
+    off = np.zeros(len(items) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(x) for x in items])
+    blob = _host_in(np.frombuffer(b"".join(items) + b"\x00", dtype=np.uint8), 0, "items")
+    offs = _host_in(off, 8, "off")
+    out = _host(32, name="out", align=1)
+    ctx.check(ctx.lib.cda_merkle_root(ctx.h, _p(blob), _p(offs, U64P), len(items), _p(out)))
+    out.assert_written(np.frombuffer(pyref.merkle_root(items), dtype=np.uint8))
+    out.assert_guards()
+    blob.assert_unchanged()
+    offs.assert_unchanged()
+
+
+@pytest.mark.gpu
+def test_square_subtree_root(ctx):
+    """cda_square_subtree_root: 90 bytes, the row root for an empty walk and
+    its two children one step down."""
+    import pyref
+    from celestia_da import proof as gpr
+    k = 4
+    ods, _, e_rows, _, _, _ = _square(k, 3)
+    sq = gpr.ResidentSquare(ods, ctx)
+    try:
+        got = []
+        for walk in ([], [0], [1]):
+            w = _host_in(np.array(walk or [0], dtype=np.uint8), 1, "walk")
+            out = _host(90, name="root", align=2)
+            ctx.check(ctx.lib.cda_square_subtree_root(sq.h, 1, _p(w), len(walk), _p(out)))
+            out.assert_guards()
+            w.assert_unchanged()
+            got.append(out.payload_host().tobytes())
+            assert got[-1] != out.pattern().tobytes()
+    finally:
+        sq.close()
+    assert got[0] == e_rows[1].tobytes()
+    assert pyref.nmt_hash_node(got[1], got[2]) == got[0]
+
+
+# ---------------------------------------------------------------------------
+# Entry points whose outputs already have an "untouched" test: guards only
+# ---------------------------------------------------------------------------
+def _guard_fields(batch, fields):
+    """Move the arrays `fields` of a proof batch into guarded host buffers
+    (same shapes and types); returns {name: Guarded}."""
+    g = {}
+    for name in fields:
+        a = getattr(batch, name)
+        stride = a.strides[0] if a.ndim and a.shape[0] else 0
+        g[name] = _host(a.nbytes, stride, name)
+        setattr(batch, name, g[name].payload().view(a.dtype).reshape(a.shape))
+    return g
+
+
+def _assert_fields(guards, ref):
+    for name, g in guards.items():
+        g.assert_written(np.ascontiguousarray(getattr(ref, name)))
+        g.assert_guards()
+
+
+@pytest.mark.gpu
+def test_resident_proofs_guarded(ctx):
+    """cda_square_share_proofs, cda_square_namespace_proofs and
+    cda_square_commitment_proofs into guarded arrays: the bytes of the plain
+    call (pinned by their own tests), nothing around any of the arrays."""
+    from celestia_da import namespace as gns
+    from celestia_da import proof as gpr
+    k = 4
+    ods = _square(k, 3)[0]
+    sq = gpr.ResidentSquare(ods, ctx)
+    try:
+        ranges = [(0, 1), (3, 6), (5, 16), (15, 16)]
+        ref = sq.share_proofs_batch(ranges)
+        b = gpr.ShareProofsBatch.empty(k, ranges)
+        g = _guard_fields(b, b.FIELDS)
+        sq.share_proofs_batch(ranges, out=b)
+        _assert_fields(g, ref)
+
+        present = sorted({ods[i, :29].tobytes() for i in range(k * k)})
+        absent = bytes(present[1][:28]) + bytes([present[1][28] ^ 1])
+        queries = [present[0], present[-1], absent, b"\x00" * 29]
+        ref = sq.namespace_proofs(queries)
+        b = gns.NamespaceProofsBatch.empty(k, queries, gns.namespace_plan(sq, queries))
+        g = _guard_fields(b, b.FIELDS)
+        sq.namespace_proofs(queries, out=b)
+        _assert_fields(g, ref)
+
+        starts, lens = [0, 5, 12], [3, 6, 4]
+        ref = sq.commitment_proofs(starts, lens, 2)
+        b = gpr.CommitmentProofsBatch.empty(k, starts, lens, 2)
+        g = _guard_fields(b, b.FIELDS)
+        sq.commitment_proofs(starts, lens, 2, out=b)
+        _assert_fields(g, ref)
+    finally:
+        sq.close()
+
+
+@pytest.mark.gpu
+def test_verifier_outputs_guarded(ctx):
+    """The verdict arrays of the five verifiers (and cda_befp_verify's rebuilt
+    roots): n bytes each, the verdicts of the plain call."""
+    import befp_ref as ref
+    from celestia_da import byzantine, sampling
+    from celestia_da import proof as gpr
+    from test_sampling import all_cells
+    k = 4
+    ods, _, e_rows, _, e_root, _ = _square(k, 3)
+    root = e_root.tobytes()
+    sq = gpr.ResidentSquare(ods, ctx)
+    try:
+        shares = sq.share_proofs_batch([(0, 1), (3, 6), (5, 16)])
+        shares.shares[1, 40] ^= 1
+        samples = sq.sample_proofs(all_cells(k)[::5])
+        samples.shares[2, 7] ^= 1
+        queries = sorted({ods[i, :29].tobytes() for i in range(k * k)})[:3]
+        names = sq.namespace_proofs(queries)
+        commits = sq.commitment_proofs([0, 5, 12], [3, 6, 4], 2)
+        commits.commitments[1, 0] ^= 1
+    finally:
+        sq.close()
+
+    def run(n, call, plain):
+        v = _host(n, 1, "verdict", align=1)
+        ctx.check(call(_p(v)))
+        v.assert_written(np.asarray(plain, dtype=np.uint8))
+        v.assert_guards()
+        return plain
+
+    b = shares.batch(root)
+    plain = run(3, lambda v: ctx.lib.cda_share_proofs_verify(ctx.h, C.byref(b), v), shares.verify(root, ctx))
+    assert plain[0] == 0 and plain[1] == 2      # valid / a tampered share
+    plain = sampling.verify_samples(samples, root, ctx)
+    assert plain[2] != 0 and plain[3] == 0
+    r, c, a = sampling.split_coords(samples.coords)
+    roots = _host_in(np.tile(e_root, len(samples)), 32, "data_roots")
+    arrs = [np.ascontiguousarray(x) for x in (samples.shares, samples.nmt_nodes, samples.axis_roots,
+                                              samples.leaf_hash, samples.aunts)]
+    run(len(samples), lambda v: ctx.lib.cda_sample_proofs_verify(
+        ctx.h, k, len(samples), _p(roots), r.ctypes.data_as(U32P), c.ctypes.data_as(U32P), a.ctypes.data_as(U8P),
+        *[x.ctypes.data_as(U8P) for x in arrs], v), plain)
+    roots.assert_unchanged()
+    nb = names.batch()
+    rr = np.ascontiguousarray(e_rows).reshape(-1)
+    run(3, lambda v: ctx.lib.cda_namespace_proofs_verify(ctx.h, k, rr.ctypes.data_as(U8P), C.byref(nb), v),
+        names.verify(e_rows, ctx))
+    cb = commits.batch(root)
+    plain = run(3, lambda v: ctx.lib.cda_commitment_proofs_verify(ctx.h, C.byref(cb), v),
+                commits.verify(root, None, ctx))
+    assert list(plain) == [0, 3, 0]             # the second commitment was tampered
+    # cda_befp_verify: verdicts and rebuilt roots
+    cs = ref.cases(2)
+    proofs, dahs = [x[1] for x in cs], [(x[2], x[3]) for x in cs]
+    plain_v, plain_r = byzantine.verify_batch(proofs, dahs, ctx)
+    bb, keep = byzantine.pack_batch(proofs, dahs)
+    v, rebuilt = _host(len(cs), 1, "verdict", align=1), _host(len(cs) * 90, 90, "rebuilt_roots", align=2)
+    ctx.check(ctx.lib.cda_befp_verify(ctx.h, C.byref(bb), _p(v), _p(rebuilt)))
+    del keep
+    v.assert_written(plain_v)
+    rebuilt.assert_written(plain_r)
+    v.assert_guards()
+    rebuilt.assert_guards()
