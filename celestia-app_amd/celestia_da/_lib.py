@@ -74,6 +74,7 @@ EXPORTED = (
     "cda_befp_build", "cda_befp_build_device", "cda_befp_batch_check", "cda_befp_verify",
     "cda_square_commitment_proofs_plan", "cda_square_commitment_proofs", "cda_commitment_proofs_verify",
     "cda_repair_batch", "cda_repair_batch_device", "cda_repair_batch_plan",
+    "cda_shares_parse_plan", "cda_shares_parse", "cda_square_parse_plan", "cda_square_parse",
 )
 # cda_namespace_proof_batch kinds (include/cda.h)
 CDA_NAMESPACE_INCLUSION = 1
@@ -212,6 +213,20 @@ class NamespaceProofBatch(C.Structure):
                 ("absence_leaf", _u8p)]
 
 
+class ParsePlanT(C.Structure):
+    """cda_parse_plan_t (include/cda.h)."""
+    _fields_ = [(n, C.c_uint32) for n in ("n_blobs", "n_txs", "n_pfbs", "n_padding_shares")] + \
+               [(n, C.c_uint64) for n in ("blob_bytes", "unit_bytes")]
+
+
+class ParseOut(C.Structure):
+    """cda_parse_out (include/cda.h)."""
+    _u8p, _u32p, _u64p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+    _fields_ = [("blob_start", _u32p), ("blob_shares", _u32p), ("blob_namespace", _u8p),
+                ("blob_share_version", _u8p), ("blob_off", _u64p), ("blob_data", _u8p), ("unit_off", _u64p),
+                ("unit_data", _u8p), ("unit_start", _u32p), ("unit_end", _u32p)]
+
+
 class BefpBatch(C.Structure):
     """cda_befp_batch (include/cda.h)."""
     _u8p, _u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
@@ -324,6 +339,10 @@ def load(path: str | None = None):
                                             u8p]
         L.cda_befp_batch_check.argtypes = [C.POINTER(BefpBatch)]
         L.cda_befp_verify.argtypes = [ctxp, C.POINTER(BefpBatch), u8p, u8p]
+        L.cda_shares_parse_plan.argtypes = [u8p, C.c_uint64, C.POINTER(ParsePlanT)]
+        L.cda_shares_parse.argtypes = [u8p, C.c_uint64, C.POINTER(ParseOut)]
+        L.cda_square_parse_plan.argtypes = [vp, u32p, u32p, C.c_uint32, C.POINTER(ParsePlanT)]
+        L.cda_square_parse.argtypes = [vp, u32p, u32p, C.c_uint32, C.POINTER(ParseOut)]
         L.cda_comm_unique_id.argtypes = [u8p]
         L.cda_comm_init.argtypes = [ctxp, C.c_int, C.c_int, u8p]
         L.cda_comm_destroy.argtypes = [ctxp]

@@ -269,6 +269,44 @@ class ResidentSquare:
                                                                  len(st), subtree_root_threshold, C.byref(o)))
         return out
 
+    @staticmethod
+    def _ranges_args(ranges):
+        """(starts, ends, n, the arrays behind the pointers) for cda_square_parse*; None: the whole square."""
+        if ranges is None:
+            return None, None, 0, None
+        r = _ranges_array(ranges)
+        if len(r) == 0:   # no range is nothing to parse, not the whole square
+            raise _lib.CdaError(_lib.CDA_ERR_INVALID, "no share range given")
+        st, en = np.ascontiguousarray(r[:, 0]), np.ascontiguousarray(r[:, 1])
+        u32p = C.POINTER(C.c_uint32)
+        return st.ctypes.data_as(u32p), en.ctypes.data_as(u32p), len(r), (st, en)
+
+    def parse_plan(self, ranges=None) -> dict:
+        """cda_square_parse_plan: the counts and byte sizes of what the square
+        (or its share ranges `ranges`, [(start, end)]) parses to."""
+        from . import shares
+        st, en, n, _alive = self._ranges_args(ranges)
+        p = _lib.ParsePlanT()
+        self.ctx.check(self.ctx.lib.cda_square_parse_plan(self.h, st, en, n, C.byref(p)))
+        return shares.plan_dict(p)
+
+    def parse(self, ranges=None, blob_data: bool = True):
+        """go-square shares.ParseShares of the original square, or of its share
+        ranges `ranges` ([(start, end)], ascending and disjoint, each parsed as
+        an input of its own), on the GPU (cda_square_parse_plan, then
+        cda_square_parse): a shares.ParsedSquare with the txs, the PFBs' raw
+        IndexWrapper bytes, the blobs with their starts and share counts and
+        the units' share ranges.  blob_data=False: the table only, the blobs'
+        data stays empty."""
+        from . import shares
+        st, en, n, _alive = self._ranges_args(ranges)
+        p = _lib.ParsePlanT()
+        self.ctx.check(self.ctx.lib.cda_square_parse_plan(self.h, st, en, n, C.byref(p)))
+        buf = shares.ParseBuffers(p, blob_data=blob_data)
+        o = buf.out_struct()
+        self.ctx.check(self.ctx.lib.cda_square_parse(self.h, st, en, n, C.byref(o)))
+        return buf.parsed()
+
     def subtree_root(self, row: int, walk) -> bytes:
         """EDSSubTreeRootCacher.getSubTreeRoot (pkg/inclusion/nmt_caching.go:111-124):
         the node of EDS row tree `row` reached by `walk` (False = WalkLeft,
@@ -1042,7 +1080,14 @@ def blob_tx_blobs(tx: bytes):
                 sizes.append(sum(len(d) for f, w, d in _pb_fields(v) if f == 2 and w == 2))
     except ValueError:
         return None
-    commits = []
+    commits = pfb_share_commitments(inner)
+    return [(inclusion.sparse_shares_needed(sz), commits[i] if i < len(commits) else None)
+            for i, sz in enumerate(sizes)]
+
+
+def pfb_share_commitments(inner: bytes) -> list:
+    """The share commitments of the MsgPayForBlobs in the signed tx `inner` (a
+    BlobTx's tx, an IndexWrapper's tx); [] when it does not decode."""
     try:   # TxRaw.body_bytes -> TxBody.messages -> Any{type_url, value} -> MsgPayForBlobs.share_commitments
         body = b"".join(v for fn, wt, v in _pb_fields(inner) if fn == 1 and wt == 2)
         for fn, wt, v in _pb_fields(body):
@@ -1050,12 +1095,10 @@ def blob_tx_blobs(tx: bytes):
                 continue
             msg = {f: d for f, w, d in _pb_fields(v) if w == 2}
             if msg.get(1) == b"/celestia.blob.v1.MsgPayForBlobs":
-                commits = [d for f, w, d in _pb_fields(msg.get(2, b"")) if f == 4 and w == 2]
-                break
+                return [d for f, w, d in _pb_fields(msg.get(2, b"")) if f == 4 and w == 2]
     except ValueError:
-        commits = []
-    return [(inclusion.sparse_shares_needed(sz), commits[i] if i < len(commits) else None)
-            for i, sz in enumerate(sizes)]
+        pass
+    return []
 
 
 def new_blob_commitment_proofs(txs, app_version: int = 2, ctx=None) -> list:
@@ -1079,3 +1122,29 @@ def new_blob_commitment_proofs(txs, app_version: int = 2, ctx=None) -> list:
     finally:
         sq.close()
     return list(zip(batch.proofs(), [c for _, c in blobs]))
+
+
+def new_blob_commitment_proofs_from_square(sq: ResidentSquare, subtree_root_threshold: int = 64) -> list:
+    """new_blob_commitment_proofs for a node that holds only the square (an EDS it
+    received, or one repaired from samples): the blobs' starts and lengths come
+    from ResidentSquare.parse (the table only, no blob bytes), the claimed
+    commitments from the MsgPayForBlobs inside the PFBs' IndexWrappers, the
+    order is the PFBs' (a PFB's blobs by its share_indexes).  One parse, one
+    cda_square_commitment_proofs call on the same resident square."""
+    from . import shares
+    parsed = sq.parse(blob_data=False)
+    share_len = dict(zip(parsed.blob_starts, parsed.blob_share_lens))
+    starts, lens, claimed = [], [], []
+    for unit in parsed.pfbs:
+        inner, idx = shares.unmarshal_index_wrapper(unit)
+        commits = pfb_share_commitments(inner)
+        for i, start in enumerate(idx):
+            if start not in share_len:
+                raise _lib.CdaError(_lib.CDA_ERR_INVALID, f"a PFB names share {start}, where no blob starts")
+            starts.append(start)
+            lens.append(share_len[start])
+            claimed.append(commits[i] if i < len(commits) else None)
+    if not starts:
+        return []
+    batch = sq.commitment_proofs(starts, lens, subtree_root_threshold)
+    return list(zip(batch.proofs(), claimed))

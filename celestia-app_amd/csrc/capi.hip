@@ -683,6 +683,45 @@ int cda_square_namespace_proofs(cda_square* sq, const uint8_t* namespaces, uint3
     });
 }
 
+int cda_shares_parse_plan(const uint8_t* shares, uint64_t n_shares, cda_parse_plan_t* out) {
+    // Host-only (no device work), no context.
+    return host_only(nullptr, [&](std::string* err) -> int {
+        if (!out) {
+            *err = "null buffer";
+            return CDA_ERR_INVALID;
+        }
+        return cda::shares_parse(shares, n_shares, out, nullptr, err);
+    });
+}
+
+int cda_shares_parse(const uint8_t* shares, uint64_t n_shares, const cda_parse_out* out) {
+    return host_only(nullptr, [&](std::string* err) -> int {
+        if (!out) {
+            *err = "null buffer";
+            return CDA_ERR_INVALID;
+        }
+        return cda::shares_parse(shares, n_shares, nullptr, out, err);
+    });
+}
+
+int cda_square_parse_plan(cda_square* sq, const uint32_t* starts, const uint32_t* ends, uint32_t n_ranges,
+                          cda_parse_plan_t* out) {
+    if (!sq) return CDA_ERR_INVALID;
+    return guarded(sq->ctx, [&](cda::Engine& e) -> int {
+        if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.square_parse(&sq->sq, starts, ends, n_ranges, out, nullptr);
+    });
+}
+
+int cda_square_parse(cda_square* sq, const uint32_t* starts, const uint32_t* ends, uint32_t n_ranges,
+                     const cda_parse_out* out) {
+    if (!sq) return CDA_ERR_INVALID;
+    return guarded(sq->ctx, [&](cda::Engine& e) -> int {
+        if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.square_parse(&sq->sq, starts, ends, n_ranges, nullptr, out);
+    });
+}
+
 int cda_namespace_proofs_verify(cda_ctx* ctx, uint32_t k, const uint8_t* row_roots,
                                 const cda_namespace_proof_batch* b, uint8_t* verdict) {
     return guarded(ctx, [&](cda::Engine& e) -> int { return e.namespace_proofs_verify(k, row_roots, b, verdict); });

@@ -24,6 +24,8 @@ struct cda_commitment_proofs_out;
 struct cda_commitment_proof_batch;
 struct cda_namespace_proof_batch;
 struct cda_befp_batch;
+struct cda_parse_plan_t;
+struct cda_parse_out;
 namespace cda {
 class OutRegions;      // out_regions.h
 struct ResidentView;   // resident_proof_dev.h
@@ -146,6 +148,11 @@ std::string befp_batch_check(const cda_befp_batch* b);
 
 // repair.hip: squares per verification chunk of a batch repair of width w (the fixed caps of include/cda.h).
 uint32_t repair_batch_chunk(uint32_t w);
+
+// parse.hip: shares.ParseShares of n contiguous host shares, host only (cda_shares_parse_plan / cda_shares_parse):
+// the sizes into *plan and / or the outputs of *out, either may be NULL; the error text into *err.
+int shares_parse(const uint8_t* shares, uint64_t n_shares, cda_parse_plan_t* plan, const cda_parse_out* out,
+                 std::string* err);
 
 // comm.hip: ncclGetUniqueId into 128 bytes (CDA_OK / CDA_ERR_DEVICE).
 int comm_unique_id(uint8_t* id);
@@ -290,7 +297,8 @@ class Engine {
     // Resident squares and proofs (proof.hip).
     int square_create(const uint8_t* ods, uint32_t k, ResidentSquare* sq);
     int square_gather(ResidentSquare* sq, const std::vector<GatherPiece>& pieces, uint8_t* out, size_t out_len);
-    int square_gather_device(ResidentSquare* sq, const std::vector<GatherPiece>& pieces, size_t out_len);
+    int square_gather_device(ResidentSquare* sq, const std::vector<GatherPiece>& pieces, size_t out_len,
+                             bool wait = true);
     int square_read(ResidentSquare* sq, ResidentSquare::Part part, uint8_t* out);   // synchronous D2H
     int square_subtree_root(ResidentSquare* sq, uint32_t row, const uint8_t* walk, uint32_t walk_len, uint8_t* out);
     int square_blob_commitments(ResidentSquare* sq, const uint32_t* starts, const uint32_t* lens, uint32_t n,
@@ -334,6 +342,11 @@ class Engine {
     int square_namespace_plan(ResidentSquare* sq, const uint8_t* namespaces, uint32_t n, cda_namespace_plan_t* out);
     int square_namespace_proofs(ResidentSquare* sq, const uint8_t* namespaces, uint32_t n,
                                 const cda_namespace_proofs_out& out);
+    // Shares of Q0 back into transactions and blobs (parse.hip): the headers of the ranges' shares come back
+    // through the gather kernel, the host builds and checks the sequence table (parse_plan.h), one more gather
+    // launch packs the raw bytes, the compact streams come back for the unit walk.  plan and out may be NULL.
+    int square_parse(ResidentSquare* sq, const uint32_t* starts, const uint32_t* ends, uint32_t n_ranges,
+                     cda_parse_plan_t* plan, const cda_parse_out* out);
     // The verifying side: the batch of share_proofs_verify built from the coordinates.
     int sample_proofs_verify(uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
                              const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,

@@ -55,11 +55,40 @@ __global__ __launch_bounds__(1024) void rfc_levels_kernel(uint32_t* __restrict__
     if (threadIdx.x < 8) reinterpret_cast<uint32_t*>(root)[threadIdx.x] = bswap32(src[threadIdx.x]);
 }
 
-// Copies of (src, len) pieces into one output buffer: one workgroup per piece.
-__global__ __launch_bounds__(256) void gather_kernel(const GatherPiece* __restrict__ pieces,
+// Copies of (src, len) pieces into one output buffer (8-byte aligned): one wavefront per piece, source and
+// destination at any byte offset.  A lane owns one aligned 8-byte window of the output per pass: it reads the
+// three aligned source words that hold the window's bytes (only those that hold a byte of the piece, so nothing
+// is read outside the aligned words of [src, src + len)), realigns them with v_alignbyte and stores the window
+// whole when it lies inside the piece, byte by byte at the piece's two ends.  Every output byte is written by
+// exactly one lane and no window is read back: a neighbouring piece owns the rest of an edge window.
+__global__ __launch_bounds__(256) void gather_kernel(const GatherPiece* __restrict__ pieces, uint32_t n_pieces,
                                                      uint8_t* __restrict__ out) {
-    const GatherPiece p = pieces[blockIdx.x];
-    for (uint32_t i = threadIdx.x; i < p.len; i += blockDim.x) out[p.dst + i] = p.src[i];
+    const uint32_t g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (g >= n_pieces) return;
+    const GatherPiece p = pieces[g];
+    const uint32_t lane = threadIdx.x & 63;
+    const int32_t len = (int32_t)p.len, lead = (int32_t)(p.dst & 7);
+    for (int32_t rel = 8 * (int32_t)lane - lead; rel < len; rel += 8 * 64) {   // the window holds piece bytes [rel, rel + 8)
+        const int32_t first = rel < 0 ? -rel : 0, last = min(8, len - rel);     // its valid bytes [first, last)
+        const uintptr_t s = reinterpret_cast<uintptr_t>(p.src) + rel;           // rel < 0: only bytes >= first are used
+        const uint32_t sh = (uint32_t)(s & 3);
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(s - sh);
+        // source word j holds window bytes [4j - sh, 4j - sh + 4)
+        uint32_t x[3];
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            const int32_t lo = 4 * j - (int32_t)sh;
+            x[j] = (lo < last && lo + 4 > first) ? q[j] : 0u;
+        }
+        const uint32_t w0 = __builtin_amdgcn_alignbyte(x[1], x[0], sh), w1 = __builtin_amdgcn_alignbyte(x[2], x[1], sh);
+        uint8_t* win = out + (p.dst - lead) + (rel + lead);
+        if (first == 0 && last == 8) {
+            *reinterpret_cast<uint2*>(win) = make_uint2(w0, w1);
+        } else {
+            const uint64_t w = (uint64_t)w1 << 32 | w0;
+            for (int32_t b = first; b < last; b++) win[b] = (uint8_t)(w >> (8 * b));
+        }
+    }
 }
 
 }  // namespace
@@ -150,17 +179,19 @@ int Engine::square_gather(ResidentSquare* sq, const std::vector<GatherPiece>& pi
     return sync(s);
 }
 
-int Engine::square_gather_device(ResidentSquare* sq, const std::vector<GatherPiece>& pieces, size_t out_len) {
+int Engine::square_gather_device(ResidentSquare* sq, const std::vector<GatherPiece>& pieces, size_t out_len,
+                                 bool wait) {
     hipStream_t s = stream_;
     CDA_TRY(ensure(sq->scratch, out_len ? out_len : 1, "hipMalloc"));
     if (pieces.empty()) return CDA_OK;
     CDA_TRY(ensure(sq->pieces, pieces.size() * sizeof(GatherPiece), "hipMalloc"));
     CDA_TRY(h2d(sq->pieces.ptr, pieces.data(), pieces.size() * sizeof(GatherPiece), s, "H2D pieces"));
-    hipLaunchKernelGGL(gather_kernel, dim3((uint32_t)pieces.size()), dim3(256), 0, s, sq->pieces.as<GatherPiece>(),
-                       sq->scratch.as<uint8_t>());
+    hipLaunchKernelGGL(gather_kernel, dim3(((uint32_t)pieces.size() + 3) / 4), dim3(256), 0, s,
+                       sq->pieces.as<GatherPiece>(), (uint32_t)pieces.size(), sq->scratch.as<uint8_t>());
     CDA_TRY(launched("gather"));
-    // `pieces` is pageable: make sure the copy has left it before returning
-    return sync(s);
+    // `pieces` is pageable: make sure the copy has left it before returning (wait = false: the caller
+    // synchronises the stream itself before it lets go of `pieces`)
+    return wait ? sync(s) : CDA_OK;
 }
 
 int Engine::regions_out(const OutRegions& out, const uint8_t* scratch, bool one_copy, hipStream_t s,

@@ -53,6 +53,10 @@
  *                          ProveNamespace's proofs (EXT nmt v0.22.0; absence proofs
  *                          included), the rows chosen as GetSharesByNamespace chooses
  *                          them from the DAH, and Proof.VerifyNamespace of the answers
+ *   cda_shares_parse_plan / cda_shares_parse / cda_square_parse_plan / cda_square_parse
+ *                          go-square shares.ParseShares / ParseTxs / ParseBlobs (EXT v1.1.0): a
+ *                          square's shares back into its transactions, IndexWrappers and blobs,
+ *                          on the host or from a resident square's Q0 on the device
  *   cda_nmt_axis_root(s) / cda_nmt_prove_range
  *                          wrapper.NewErasuredNamespacedMerkleTree + Push +
  *                          Root / ProveRange (pkg/wrapper/nmt_wrapper.go:55-129)
@@ -778,6 +782,69 @@ typedef struct cda_commitment_proof_batch {
     uint32_t n_aunts;
 } cda_commitment_proof_batch;
 int cda_commitment_proofs_verify(cda_ctx *ctx, const cda_commitment_proof_batch *b, uint8_t *verdict);
+
+/* ---- Shares back into transactions and blobs -------------------------------------
+ * The way back from a square: go-square v1.1.0 shares.ParseShares / ParseTxs / ParseBlobs (parseCompactShares,
+ * parseSparseShares), restated from their published algorithms and specs/src/specs/shares.md (go-square is not
+ * vendored; what pins this code is that spec, mainnet block 408 and the square builder).
+ * The input is n shares of 512 bytes in order.  Per share: namespace = bytes [0, 29), info = byte 29, version =
+ * info >> 1, start = info & 1.  A start share opens a sequence and closes the one before it, a continuation
+ * extends the open one; the sequence length L is the big-endian word at [30, 34) of the start share.
+ *   padding  a start share with L = 0 in any namespace, or one in the tail-padding or primary-reserved-padding
+ *            namespace: one share, skipped and counted (n_padding_shares);
+ *   compact  TX or PFB namespace: raw data [38, 512) of the start share and [34, 512) of a continuation, the four
+ *            bytes in front being the share's reserved bytes;
+ *   sparse   every other namespace, a blob: [34, 512) of the start share (478 bytes), [30, 512) of a continuation.
+ * A blob is its namespace, share version, the first L bytes of its concatenated raw data, its first share and its
+ * share count.  A compact sequence's stream is the first L bytes of its raw data: a uvarint of at most 10 bytes,
+ * then that many bytes as one unit, until the stream ends or a uvarint of 0.  A unit reports the shares [start,
+ * end) that hold it, length prefix included (for distinct txs what cda_square_tx_share_ranges returns).
+ * Errors, CDA_ERR_SQUARE with a message naming the share, outputs untouched, the first in share order:
+ *   "share 5: parity-namespace share"; "share 5: unsupported share version 1";
+ *   "share 0: the first share of the input is a continuation share" (of a range: "... of range 2 is ...");
+ *   "share 5: continuation share's namespace differs from that of its sequence's start share 3";
+ *   "sequence at share 3: length 961 needs 3 shares, found 2" when a sequence closes (sparse:
+ *     SparseSharesNeeded(L); compact: 1 for L <= 474, else 1 + ceil((L - 474) / 478); padding: 1);
+ * then, per compact sequence, TX sequences first:
+ *   "share 1: malformed unit length prefix"; "share 1: unit of 700 bytes runs past the sequence length 600"
+ *     (the share holding the prefix's first byte; go-square stops silently at both);
+ *   "share 2: reserved bytes 0, expected 38": every compact share's reserved bytes must be the offset in the share
+ *     of the first unit whose length prefix starts in it, or 0 if none does (go-square does not check them;
+ *     square.Construct always writes them so).
+ * The zero fill after the data is not checked (go-square does not either).
+ *
+ * cda_shares_parse_plan / cda_shares_parse: host only, no context (the text through cda_last_error(NULL)); the C
+ * restatement, and the yardstick of the device calls.  n_shares == 0: CDA_OK, all sizes zero.
+ * cda_square_parse_plan / cda_square_parse: the same over the original square of a resident square, on the
+ * device: the first 40 bytes of every share come back through the resident squares' gather kernel (one wavefront
+ * per piece, aligned 8-byte stores, byte stores only at a piece's two ends), the sequence table is built and
+ * checked on the host, one more launch of that kernel packs the raw bytes (one piece per source share), the
+ * compact streams come back for the unit walk.  starts / ends: n_ranges share ranges [starts[i], ends[i]) of the
+ * original square, row-major, ascending and disjoint (CDA_ERR_INVALID naming the range otherwise), each parsed as
+ * an input of its own: a range that begins at a continuation share or ends inside a sequence fails under the
+ * rules above.  n_ranges == 0 (both NULL): the whole k x k square.  blob_start, unit_start and unit_end are
+ * indexes into the original square.  A square created with CDA_ERR_PUSH_ORDER parses like any other: share format
+ * does not depend on namespace order.  Like the namespace calls, cda_square_parse keeps no state from the plan
+ * call and reads the headers again.  Host buffers, complete when the call returns. */
+typedef struct cda_parse_plan_t {
+    uint32_t n_blobs, n_txs, n_pfbs, n_padding_shares;
+    uint64_t blob_bytes, unit_bytes;
+} cda_parse_plan_t;
+typedef struct cda_parse_out {      /* any pointer may be NULL */
+    uint32_t *blob_start, *blob_shares;           /* n_blobs each */
+    uint8_t *blob_namespace, *blob_share_version; /* n_blobs*29, n_blobs */
+    uint64_t *blob_off;                           /* n_blobs+1 */
+    uint8_t *blob_data;                           /* blob_bytes, packed, no gaps */
+    uint64_t *unit_off;                           /* n_txs+n_pfbs+1 */
+    uint8_t *unit_data;                           /* unit_bytes; txs first, then PFBs (IndexWrapper bytes) */
+    uint32_t *unit_start, *unit_end;              /* n_txs+n_pfbs each: share range of each unit */
+} cda_parse_out;
+int cda_shares_parse_plan(const uint8_t *shares, uint64_t n_shares, cda_parse_plan_t *out);
+int cda_shares_parse(const uint8_t *shares, uint64_t n_shares, const cda_parse_out *out);
+int cda_square_parse_plan(cda_square *sq, const uint32_t *starts, const uint32_t *ends, uint32_t n_ranges,
+                          cda_parse_plan_t *out);
+int cda_square_parse(cda_square *sq, const uint32_t *starts, const uint32_t *ends, uint32_t n_ranges,
+                     const cda_parse_out *out);
 
 /* ---- Repair ------------------------------------------
  * rsmt2d ExtendedDataSquare.Repair(rowRoots, colRoots) (EXT v0.14.0,
