@@ -75,7 +75,12 @@ EXPORTED = (
     "cda_square_commitment_proofs_plan", "cda_square_commitment_proofs", "cda_commitment_proofs_verify",
     "cda_repair_batch", "cda_repair_batch_device", "cda_repair_batch_plan",
     "cda_shares_parse_plan", "cda_shares_parse", "cda_square_parse_plan", "cda_square_parse",
+    "cda_square_set_create", "cda_square_set_create_device", "cda_square_set_destroy", "cda_square_set_info",
+    "cda_square_set_at", "cda_square_set_dah", "cda_square_set_sample_proofs",
 )
+# cda_square_set_create source kinds (include/cda.h)
+CDA_SET_FROM_ODS = 0
+CDA_SET_FROM_EDS = 1
 # cda_namespace_proof_batch kinds (include/cda.h)
 CDA_NAMESPACE_INCLUSION = 1
 CDA_NAMESPACE_ABSENCE = 2
@@ -343,6 +348,14 @@ def load(path: str | None = None):
         L.cda_shares_parse.argtypes = [u8p, C.c_uint64, C.POINTER(ParseOut)]
         L.cda_square_parse_plan.argtypes = [vp, u32p, u32p, C.c_uint32, C.POINTER(ParsePlanT)]
         L.cda_square_parse.argtypes = [vp, u32p, u32p, C.c_uint32, C.POINTER(ParseOut)]
+        L.cda_square_set_create.argtypes = [ctxp, u8p, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(vp)]
+        L.cda_square_set_create_device.argtypes = [ctxp, vp, C.c_int, C.c_uint32, C.c_uint32, vp, C.POINTER(vp)]
+        L.cda_square_set_destroy.argtypes = [vp]
+        L.cda_square_set_info.argtypes = [vp, u32p, u32p]
+        L.cda_square_set_at.argtypes = [vp, C.c_uint32, C.POINTER(vp)]
+        L.cda_square_set_dah.argtypes = [vp, u8p, u8p, u8p, i32p]
+        L.cda_square_set_sample_proofs.argtypes = [vp, u32p, u32p, u32p, u8p, C.c_uint32, u8p, u8p, u8p, u8p, u8p,
+                                                   u8p]
         L.cda_comm_unique_id.argtypes = [u8p]
         L.cda_comm_init.argtypes = [ctxp, C.c_int, C.c_int, u8p]
         L.cda_comm_destroy.argtypes = [ctxp]

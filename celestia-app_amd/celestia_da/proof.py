@@ -155,10 +155,21 @@ class ResidentSquare:
         self.ctx.check(self.ctx.lib.cda_square_dah(self.h, C.byref(k), None, None, None, None))
         self.k = k.value
 
+    @classmethod
+    def _borrowed(cls, owner: "ResidentSquareSet", handle, push_order_error: bool) -> "ResidentSquare":
+        """A member of a ResidentSquareSet (cda_square_set_at): the handle is
+        the set's, and the object keeps the set alive."""
+        sq = object.__new__(cls)
+        sq.ctx, sq.h, sq.k, sq.owner = owner.ctx, handle, owner.k, owner
+        sq.push_order_error = push_order_error
+        return sq
+
     def close(self):
         if getattr(self, "h", None):
-            self.ctx.lib.cda_square_destroy(self.h)
+            if getattr(self, "owner", None) is None:   # a member's handle ends with its set
+                self.ctx.lib.cda_square_destroy(self.h)
             self.h = None
+            self.owner = None
 
     def __del__(self):
         try:
@@ -315,6 +326,139 @@ class ResidentSquare:
         out = np.empty(90, dtype=np.uint8)
         self.ctx.check(self.ctx.lib.cda_square_subtree_root(self.h, row, ptr(w), len(walk), ptr(out)))
         return out.tobytes()
+
+
+class ResidentSquareSet:
+    """n extended squares of one width kept on the GPU, built in one
+    submission (cda_square_set_*): from host arrays (from_ods, from_eds) or
+    from a batch already in HBM (from_device_ods, from_device_eds) -- the output
+    of Context.extend_dah_device, replay or rsmt2d.repair_batch_device.
+    `set[i]` is a ResidentSquare that borrows from the set and keeps it alive;
+    sampling.sample_proofs_set answers samples of many members in one launch.
+
+    An EDS source is hashed as it is (no Reed-Solomon work, the parity is not
+    checked): compare dah()'s data roots with the ones you trust.  A square
+    whose ODS is out of push order stays in the set with its blind roots:
+    `status[i]` is CDA_ERR_PUSH_ORDER and `push_order_error` is set."""
+
+    def __init__(self, ctx, handle, rc):
+        import weakref
+        self.ctx, self.h = ctx, handle
+        self.push_order_error = rc == _lib.CDA_ERR_PUSH_ORDER
+        k, n = C.c_uint32(), C.c_uint32()
+        self.ctx.check(self.ctx.lib.cda_square_set_info(self.h, C.byref(k), C.byref(n)))
+        self.k, self.n = k.value, n.value
+        self._members = weakref.WeakSet()
+        self.status = np.zeros(self.n, dtype=np.int32)
+        self.ctx.check(self.ctx.lib.cda_square_set_dah(self.h, None, None, None,
+                                                       self.status.ctypes.data_as(C.POINTER(C.c_int32))))
+
+    @classmethod
+    def _create(cls, ctx, src, d_src, kind, k, n, stream=None):
+        ctx = ctx or default_context()
+        h = C.c_void_p()
+        if d_src is None:
+            rc = ctx.lib.cda_square_set_create(ctx.h, ptr(src), kind, k, n, C.byref(h))
+        else:
+            rc = ctx.lib.cda_square_set_create_device(ctx.h, d_src, kind, k, n, stream, C.byref(h))
+        if rc not in (_lib.CDA_OK, _lib.CDA_ERR_PUSH_ORDER):
+            ctx.check(rc)
+        return cls(ctx, h, rc)
+
+    @staticmethod
+    def _host_batch(a, eds: bool):
+        """(contiguous uint8 array, k, n) of a batch of squares: (n, w, w, 512), (n, w*w, 512) or (n, w*w*512)."""
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.uint8))
+        if a.ndim < 2 or a.shape[0] == 0:
+            raise ValueError("a batch of squares has the shape (n, ...) with n >= 1")
+        n = a.shape[0]
+        cells = a[0].size // SHARE_SIZE
+        w = 1
+        while w * w < cells:
+            w *= 2
+        if w * w * SHARE_SIZE != a[0].size or (eds and w < 2):
+            raise ValueError(f"{a[0].size} bytes per square are no square of 512-byte shares")
+        return a, (w // 2 if eds else w), n
+
+    @classmethod
+    def from_ods(cls, ods, ctx=None) -> "ResidentSquareSet":
+        """n original squares on the host: extended and hashed in one submission."""
+        a, k, n = cls._host_batch(ods, False)
+        return cls._create(ctx, a, None, _lib.CDA_SET_FROM_ODS, k, n)
+
+    @classmethod
+    def from_eds(cls, eds, ctx=None) -> "ResidentSquareSet":
+        """n extended squares on the host: hashed as they are."""
+        a, k, n = cls._host_batch(eds, True)
+        return cls._create(ctx, a, None, _lib.CDA_SET_FROM_EDS, k, n)
+
+    @staticmethod
+    def _device_ptr(d, nbytes: int) -> int:
+        if hasattr(d, "data_ptr"):
+            if not d.is_contiguous() or d.numel() * d.element_size() != nbytes:
+                raise ValueError(f"the tensor must hold {nbytes} contiguous bytes")
+            d = d.data_ptr()
+        return int(d)
+
+    @classmethod
+    def from_device_ods(cls, d_ods, k: int, n: int, stream=None, ctx=None) -> "ResidentSquareSet":
+        """n original squares in HBM (a device pointer or anything with
+        data_ptr, n * k * k * 512 contiguous bytes, 16-byte aligned), read
+        only; the work is ordered after `stream` (None: the null stream)."""
+        return cls._create(ctx, None, cls._device_ptr(d_ods, n * k * k * SHARE_SIZE), _lib.CDA_SET_FROM_ODS, k, n,
+                           stream)
+
+    @classmethod
+    def from_device_eds(cls, d_eds, k: int, n: int, stream=None, ctx=None) -> "ResidentSquareSet":
+        """n extended squares in HBM (n * (2k)^2 * 512 contiguous bytes), copied
+        and hashed as they are; as from_device_ods otherwise."""
+        return cls._create(ctx, None, cls._device_ptr(d_eds, n * 4 * k * k * SHARE_SIZE), _lib.CDA_SET_FROM_EDS, k,
+                           n, stream)
+
+    def __len__(self) -> int:
+        return self.n
+
+    def __getitem__(self, i: int) -> ResidentSquare:
+        if not self.h:
+            raise _lib.CdaError(_lib.CDA_ERR_INVALID, "the square set is closed")
+        i = int(i)
+        if i < 0:
+            i += self.n
+        if not 0 <= i < self.n:
+            raise IndexError(f"square {i} of a set of {self.n}")
+        m = C.c_void_p()
+        self.ctx.check(self.ctx.lib.cda_square_set_at(self.h, i, C.byref(m)))
+        sq = ResidentSquare._borrowed(self, m, self.status[i] == _lib.CDA_ERR_PUSH_ORDER)
+        self._members.add(sq)
+        return sq
+
+    def dah(self):
+        """(row_roots, col_roots, data_roots) as uint8 arrays of shape (n, 2k, 90), (n, 2k, 90) and (n, 32)."""
+        W = 2 * self.k
+        rows = np.empty((self.n, W, NMT_ROOT_SIZE), dtype=np.uint8)
+        cols = np.empty((self.n, W, NMT_ROOT_SIZE), dtype=np.uint8)
+        roots = np.empty((self.n, 32), dtype=np.uint8)
+        self.ctx.check(self.ctx.lib.cda_square_set_dah(self.h, ptr(rows), ptr(cols), ptr(roots), None))
+        return rows, cols, roots
+
+    def sample_proofs(self, coords, out=None):
+        """sampling.sample_proofs_set(self, coords, out)."""
+        from . import sampling
+        return sampling.sample_proofs_set(self, coords, out)
+
+    def close(self):
+        """Ends the set and its members: a ResidentSquare taken from it is closed too."""
+        if getattr(self, "h", None):
+            for sq in list(self._members):
+                sq.h, sq.owner = None, None
+            self.ctx.lib.cda_square_set_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 # ------------------------------------------------- proofs of many ranges at once

@@ -112,34 +112,50 @@ def _stage_txs(blocks):
     return pinned, host, lay
 
 
+@dataclass
+class KeptSquares:
+    """One replayed batch kept resident (replay(..., keep=True)): square j of
+    `squares` is block `blocks[j]` of the replayed list."""
+    blocks: list
+    squares: "object"                 # proof.ResidentSquareSet
+
+
 def replay(blocks, data_hashes=None, max_square_size: int = SQUARE_SIZE_UPPER_BOUND,
            subtree_root_threshold: int = SUBTREE_ROOT_THRESHOLD, ctx=None, device=None, max_batch: int = 1024,
-           max_stage_bytes: int = 1 << 31):
+           max_stage_bytes: int = 1 << 31, keep: bool = False):
     """ProcessProposal's DA check for every block of `blocks` (each a list of
     tx bytes, in block order).  `data_hashes` (optional): the headers'
     DataHash per block.  Blocks of one square size go to the GPU in batches
     of at most `max_batch` squares (config 4's 1 024 at k = 128: 40 GiB of
     ODS + EDS); the blocks are staged in windows of at most `max_stage_bytes`
-    of txs (page-locked host memory).  Returns one BlockResult per block."""
+    of txs (page-locked host memory).  Returns one BlockResult per block.
+
+    keep=True: the squares stay resident to be served.  Every batch's device
+    EDS becomes a proof.ResidentSquareSet (CDA_SET_FROM_EDS: hashed where it
+    lies, no second extension, no copy to the host), unordered squares
+    included with their blind roots, and the call returns (results, kept)
+    with kept = {square size: [KeptSquares]} -- one entry per batch of that
+    size, a single one unless max_batch or max_stage_bytes split it."""
     import torch
     ctx = ctx or default_context()
     dev = torch.device("cuda", torch.cuda.current_device() if device is None else device)
     blocks = list(blocks)
     out, w0, size = [], 0, 0
+    kept = {} if keep else None
     for i, txs in enumerate(blocks):
         b = sum(map(len, txs)) + 32
         if i > w0 and size + b > max_stage_bytes:
-            out += _replay_window(blocks[w0:i], max_square_size, subtree_root_threshold, ctx, dev, max_batch)
+            out += _replay_window(blocks[w0:i], max_square_size, subtree_root_threshold, ctx, dev, max_batch, kept, w0)
             w0, size = i, 0
         size += b
-    out += _replay_window(blocks[w0:], max_square_size, subtree_root_threshold, ctx, dev, max_batch)
+    out += _replay_window(blocks[w0:], max_square_size, subtree_root_threshold, ctx, dev, max_batch, kept, w0)
     if data_hashes is not None:
         for r, h in zip(out, data_hashes):
             r.accepted = r.error is None and r.data_root == bytes(h)
-    return out
+    return (out, kept) if keep else out
 
 
-def _replay_window(blocks, max_square_size, subtree_root_threshold, ctx, dev, max_batch):
+def _replay_window(blocks, max_square_size, subtree_root_threshold, ctx, dev, max_batch, kept=None, first=0):
     import torch
     if not blocks:
         return []
@@ -183,6 +199,10 @@ def _replay_window(blocks, max_square_size, subtree_root_threshold, ctx, dev, ma
                 out[i].data_root = rt[j].tobytes()
             else:
                 out[i].error = _push_order_message(d_ods[j].cpu().numpy(), k, ctx.push_order_detail_at(j))
+        if kept is not None:   # after the messages: the set's build takes over the context's push-order words
+            from .proof import ResidentSquareSet
+            kept.setdefault(k, []).append(KeptSquares(
+                [first + i for i in idx], ResidentSquareSet.from_device_eds(d_eds, k, n, stream=stream, ctx=ctx)))
         del d_ods, d_eds
     torch.cuda.current_stream(dev).synchronize()   # the pinned staging outlives every read of it
     return out

@@ -132,6 +132,79 @@ def sample_proofs(sq, coords, out: SampleBatch | None = None) -> SampleBatch:
     return b
 
 
+@dataclass
+class SetSamples:
+    """The answer to samples across a proof.ResidentSquareSet
+    (cda_square_set_sample_proofs): ONE flat SampleBatch in request order --
+    what verify_samples takes, with data_roots(...) as its per-sample roots --
+    and the square each sample came from."""
+    batch: SampleBatch
+    squares: np.ndarray      # (n,) uint32: the member each sample names
+
+    def __len__(self) -> int:
+        return len(self.batch)
+
+    def data_roots(self, set_roots) -> np.ndarray:
+        """One data root per sample, (n, 32), from the set's (n_squares, 32) data roots."""
+        return np.ascontiguousarray(np.asarray(set_roots, dtype=np.uint8).reshape(-1, 32)[self.squares])
+
+    def by_square(self, verdicts=None):
+        """[(square, SampleBatch)] -- with `verdicts`, [(square, SampleBatch,
+        verdicts of that batch)] -- one entry per square named, ascending: the
+        per-square batches assemble_batch takes.  When the requests are grouped
+        by square (the square column is non-decreasing) every batch is a view
+        of the flat arrays, no byte is copied; otherwise the samples of a
+        square are gathered."""
+        sq = self.squares
+        v = None if verdicts is None else np.asarray(verdicts).reshape(-1)
+        if v is not None and v.size != len(self):
+            raise ValueError(f"{len(self)} samples but {v.size} verdicts")
+        grouped = bool(np.all(sq[1:] >= sq[:-1]))
+        out = []
+        for s in np.unique(sq).tolist():
+            if grouped:
+                lo, hi = np.searchsorted(sq, s, "left"), np.searchsorted(sq, s, "right")
+                pick = slice(int(lo), int(hi))
+            else:
+                pick = np.nonzero(sq == s)[0]
+            b = SampleBatch(self.batch.k, self.batch.coords[pick], *(a[pick] for a in self.batch.arrays()))
+            out.append((s, b) if v is None else (s, b, v[pick]))
+        return out
+
+
+def split_set_coords(coords):
+    """(squares, rows, cols, axes) from an (n, 4) integer array of (square,
+    row, col, axis), or (n, 3) of (square, row, col): every sample on the row
+    axis.  As split_coords for the values a uint32 / uint8 cannot carry."""
+    c = np.asarray(coords, dtype=np.int64)
+    if c.size == 0:
+        c = c.reshape(0, 4)
+    if c.ndim != 2 or c.shape[1] not in (3, 4):
+        raise ValueError("coords must be an (n, 4) array of (square, row, col, axis) or an (n, 3) array of "
+                         "(square, row, col)")
+    bad = np.nonzero((c[:, 0] < 0) | (c[:, 0] >= 1 << 32))[0]
+    if bad.size:
+        raise _lib.CdaError(_lib.CDA_ERR_INVALID, f"sample {bad[0]}: square {c[bad[0], 0]} out of range")
+    return (np.ascontiguousarray(c[:, 0], dtype=np.uint32),) + split_coords(c[:, 1:])
+
+
+def sample_proofs_set(sqset, coords, out: SampleBatch | None = None) -> SetSamples:
+    """cda_square_set_sample_proofs on a proof.ResidentSquareSet: the samples
+    `coords` -- rows of (square, row, col, axis) -- of any number of members
+    in one launch.  Returns SetSamples: the flat batch in request order plus
+    the square column.  `out` (SampleBatch.empty(k, coords[:, 1:])) receives
+    the answer in place."""
+    squares, rows, cols, axes = split_set_coords(coords)
+    c = np.asarray(coords, dtype=np.int64)
+    c = c.reshape(0, 4) if c.size == 0 else c
+    b = out if out is not None else SampleBatch.empty(sqset.k, c[:, 1:])
+    if len(b) != rows.size or b.k != sqset.k:
+        raise ValueError("output batch does not match the coordinates")
+    sqset.ctx.check(sqset.ctx.lib.cda_square_set_sample_proofs(sqset.h, _u32p(squares), _u32p(rows), _u32p(cols),
+                                                               ptr(axes), rows.size, *(ptr(a) for a in b.arrays())))
+    return SetSamples(b, squares)
+
+
 def verify_samples(batch: SampleBatch, data_root, ctx=None) -> np.ndarray:
     """cda_sample_proofs_verify: a uint8 verdict per sample -- 0 valid, 1 the
     axis root does not verify against the data root, 2 the cell does not verify

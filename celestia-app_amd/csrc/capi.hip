@@ -4,7 +4,9 @@
 // ABI.
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
+#include <string>
 #include <thread>
 #include <utility>
 
@@ -22,6 +24,13 @@ struct cda_ctx {
 struct cda_square {
     cda_ctx* ctx;
     cda::ResidentSquare sq;
+    cda_square_set* owner = nullptr;   // a member of a set: borrowed, ends with the set
+};
+
+struct cda_square_set {
+    cda_ctx* ctx;
+    cda::ResidentSquareSet set;
+    std::vector<std::unique_ptr<cda_square>> members;   // one per square, views into the set's arenas
 };
 
 namespace {
@@ -547,6 +556,11 @@ int cda_square_create(cda_ctx* ctx, const uint8_t* ods, uint32_t n_shares, cda_s
 
 int cda_square_destroy(cda_square* sq) {
     if (!sq) return CDA_OK;
+    if (sq->owner)
+        return guarded(sq->ctx, [&](cda::Engine& e) -> int {
+            return e.fail(CDA_ERR_INVALID, "the square is a member of a cda_square_set and ends with it: "
+                                           "call cda_square_set_destroy on the set");
+        });
     std::lock_guard<std::mutex> g(sq->ctx->eng.mutex());
     DeviceScope dev(sq->ctx->eng.device());
     // no queued work of the context reads the square any more: the square's
@@ -609,6 +623,93 @@ int cda_square_sample_proofs(cda_square* sq, const uint32_t* rows, const uint32_
     return guarded(sq->ctx, [&](cda::Engine& e) -> int {
         const cda::Engine::SampleOut o{shares, namespaces, nmt_nodes, axis_roots, leaf_hash, aunts};
         return e.square_sample_proofs(&sq->sq, rows, cols, axes, n, o);
+    });
+}
+
+// Both create calls: src on the host or d_src on the device.
+static int square_set_create(cda_ctx* ctx, const uint8_t* src, const void* d_src, int kind, uint32_t k, uint32_t n,
+                             void* stream, bool device, cda_square_set** out) {
+    if (!out) return CDA_ERR_INVALID;
+    *out = nullptr;
+    auto run = [&](cda::Engine& e, hipStream_t s) -> int {
+        if (kind != CDA_SET_FROM_ODS && kind != CDA_SET_FROM_EDS)
+            return e.fail(CDA_ERR_INVALID, "unknown source kind of a square set");
+        if (!cda::is_pow2(k) || k > 1024)
+            return e.fail(CDA_ERR_INVALID, "square width must be a power of two <= 1024");
+        if (n == 0) return e.fail(CDA_ERR_INVALID, "a square set holds at least one square");
+        if (n > CDA_SET_MAX_SQUARES) return e.fail(CDA_ERR_INVALID, "a square set holds at most 65535 squares");
+        if (device ? !d_src : !src) return e.fail(CDA_ERR_INVALID, "null buffer");
+        if (device && (reinterpret_cast<uintptr_t>(d_src) & 15))
+            return e.fail(CDA_ERR_INVALID, "device_src must be 16-byte aligned");
+        std::unique_ptr<cda_square_set> h(new cda_square_set{ctx, {}, {}});
+        const int rc = e.square_set_create(src, static_cast<const uint8_t*>(d_src), kind, k, n, &h->set, s);
+        if (rc != CDA_OK && rc != CDA_ERR_PUSH_ORDER) return rc;
+        h->members.reserve(n);
+        for (uint32_t i = 0; i < n; i++) {
+            h->members.emplace_back(new cda_square{ctx, {}, h.get()});
+            h->set.lend(i, &h->members.back()->sq);
+        }
+        *out = h.release();   // unordered squares stay in the set with their blind roots
+        return rc;
+    };
+    if (device) return guarded_stream(ctx, stream, run);
+    return guarded(ctx, [&](cda::Engine& e) -> int { return run(e, e.stream()); });
+}
+
+int cda_square_set_create(cda_ctx* ctx, const uint8_t* src, int kind, uint32_t k, uint32_t n, cda_square_set** out) {
+    return square_set_create(ctx, src, nullptr, kind, k, n, nullptr, false, out);
+}
+
+int cda_square_set_create_device(cda_ctx* ctx, const void* device_src, int kind, uint32_t k, uint32_t n, void* stream,
+                                 cda_square_set** out) {
+    return square_set_create(ctx, nullptr, device_src, kind, k, n, stream, true, out);
+}
+
+int cda_square_set_destroy(cda_square_set* set) {
+    if (!set) return CDA_OK;
+    std::lock_guard<std::mutex> g(set->ctx->eng.mutex());
+    DeviceScope dev(set->ctx->eng.device());
+    // as cda_square_destroy: every call on the set or a member ended with the context's end event
+    (void)set->ctx->eng.wait_last_call();
+    delete set;   // the members first (their own scratch), then the arenas
+    return CDA_OK;
+}
+
+int cda_square_set_info(cda_square_set* set, uint32_t* k, uint32_t* n) {
+    if (!set) return CDA_ERR_INVALID;
+    if (k) *k = set->set.k;
+    if (n) *n = set->set.n;
+    return CDA_OK;
+}
+
+int cda_square_set_at(cda_square_set* set, uint32_t i, cda_square** member) {
+    if (!set || !member) return CDA_ERR_INVALID;
+    *member = nullptr;
+    return guarded(set->ctx, [&](cda::Engine& e) -> int {
+        if (i >= set->set.n)
+            return e.fail(CDA_ERR_INVALID, "square " + std::to_string(i) + " is not below the set's " +
+                                               std::to_string(set->set.n) + " squares");
+        *member = set->members[i].get();
+        return CDA_OK;
+    });
+}
+
+int cda_square_set_dah(cda_square_set* set, uint8_t* row_roots, uint8_t* col_roots, uint8_t* data_roots,
+                       int32_t* status) {
+    if (!set) return CDA_ERR_INVALID;
+    return guarded(set->ctx, [&](cda::Engine& e) -> int {
+        return e.square_set_dah(&set->set, row_roots, col_roots, data_roots, status);
+    });
+}
+
+int cda_square_set_sample_proofs(cda_square_set* set, const uint32_t* squares, const uint32_t* rows,
+                                 const uint32_t* cols, const uint8_t* axes, uint32_t n, uint8_t* shares,
+                                 uint8_t* namespaces, uint8_t* nmt_nodes, uint8_t* axis_roots, uint8_t* leaf_hash,
+                                 uint8_t* aunts) {
+    if (!set) return CDA_ERR_INVALID;
+    return guarded(set->ctx, [&](cda::Engine& e) -> int {
+        const cda::Engine::SampleOut o{shares, namespaces, nmt_nodes, axis_roots, leaf_hash, aunts};
+        return e.square_set_sample_proofs(&set->set, squares, rows, cols, axes, n, o);
     });
 }
 

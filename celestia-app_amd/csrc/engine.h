@@ -130,11 +130,30 @@ struct ResidentSquare {
     enum Part { kRowRoots, kColRoots, kDataRoot, kEds };
     uint32_t k = 0, log_w = 0, push_err = push_order::kOrdered;
     DevBuf eds, levels, col_levels, roots_slots, rfc, rows, cols, root, err, scratch, pieces;
+    // a member of a ResidentSquareSet: every buffer but scratch and pieces is a view into the set's arenas
+    bool borrowed = false;
     uint64_t level_offset(uint32_t L) const;       // bytes into `levels`, L >= 0
     uint64_t col_level_offset(uint32_t L) const;   // bytes into `col_levels`, L >= 1
     ResidentView view() const;                     // what the proof kernels read
     ~ResidentSquare();
 };
+// n resident squares of one width built in one submission (square_set.hip): one arena per part, square y of
+// an arena at base + y * its stride (bytes, 64-bit), the content of a stride exactly what square_create keeps
+// in the buffer of the same name.  Every stride but the packed roots' is a multiple of 16 bytes.
+struct ResidentSquareSet {
+    uint32_t k = 0, log_w = 0, n = 0;
+    DevBuf eds, levels, col_levels, roots_slots, rfc, rows, cols, roots, err, scratch;
+    uint64_t eds_sq = 0, levels_sq = 0, col_levels_sq = 0, roots_slots_sq = 0, rfc_sq = 0, axis_roots_sq = 0;
+    std::vector<uint32_t> push_err;   // the squares' push-order words
+    void lend(uint32_t i, ResidentSquare* sq) const;   // square i's views into *sq (borrowed)
+    ~ResidentSquareSet();
+};
+// proof.hip: the data-root trees of n_squares squares in one launch, a workgroup per square: the RFC-6962 leaf
+// digests of square y's n_items root slots (root_slots + y * slots_sq bytes; a power of two >= 4) and every
+// level above them into rfc + y * rfc_sq_words (level l at entry 2 n_items - (2 n_items >> l)), the root's
+// bytes to data_roots + 32 y.
+hipError_t launch_rfc_levels_set(const uint8_t* root_slots, uint64_t slots_sq, uint32_t n_items, uint32_t n_squares,
+                                 uint32_t* rfc, uint64_t rfc_sq_words, uint8_t* data_roots, hipStream_t s);
 // One copy out of a resident square: len bytes at src (device) to byte dst of the gathered output.
 struct GatherPiece {
     const uint8_t* src;
@@ -347,6 +366,17 @@ class Engine {
     // launch packs the raw bytes, the compact streams come back for the unit walk.  plan and out may be NULL.
     int square_parse(ResidentSquare* sq, const uint32_t* starts, const uint32_t* ends, uint32_t n_ranges,
                      cda_parse_plan_t* plan, const cda_parse_out* out);
+    // Sets of resident squares (square_set.hip).  square_set_create: n squares from a host (src) or device
+    // (d_src) batch of ODSs (kind CDA_SET_FROM_ODS: extended here) or EDSs (CDA_SET_FROM_EDS: hashed as they
+    // are), every launch over all n squares, on s; complete on return.  The push-order words also become the
+    // context's last device batch (device_push_order_detail).  CDA_ERR_PUSH_ORDER leaves a usable set.
+    int square_set_create(const uint8_t* src, const uint8_t* d_src, int kind, uint32_t k, uint32_t n,
+                          ResidentSquareSet* set, hipStream_t s);
+    // Packed roots [n][2k][90] twice, data roots [n][32], status [n]; any may be NULL.
+    int square_set_dah(ResidentSquareSet* set, uint8_t* rows, uint8_t* cols, uint8_t* roots, int32_t* status);
+    // square_sample_proofs across the set (sample.hip): sample i of member squares[i], one launch.
+    int square_set_sample_proofs(ResidentSquareSet* set, const uint32_t* squares, const uint32_t* rows,
+                                 const uint32_t* cols, const uint8_t* axes, uint32_t n, const SampleOut& out);
     // The verifying side: the batch of share_proofs_verify built from the coordinates.
     int sample_proofs_verify(uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
                              const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,

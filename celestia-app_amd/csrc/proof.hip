@@ -36,9 +36,30 @@ namespace {
 
 // All RFC-6962 levels of the data-root tree (n leaf digests, n a power of two)
 // in one workgroup: level 0 = the leaf digests, level l has n >> l entries.
-__global__ __launch_bounds__(1024) void rfc_levels_kernel(uint32_t* __restrict__ lv, uint32_t n,
-                                                          uint8_t* __restrict__ root) {
-    uint32_t* src = lv;
+// One workgroup per square (blockIdx.x): square y's levels at lv + y * lv_sq
+// words, its root at root + 32 y.  kFromSlots (sets of squares, square_set.hip):
+// the workgroup first hashes level 0 itself from the square's n root slots at
+// slots + y * slots_sq bytes, so a whole set's trees are one launch; otherwise
+// level 0 is there already (launch_rfc_leaves).  A level is read back from
+// global memory by other threads of the workgroup after the barrier.
+template <bool kFromSlots>
+__global__ __launch_bounds__(kFromSlots ? 256 : 1024) void rfc_levels_kernel(
+    uint32_t* __restrict__ lv, uint64_t lv_sq, uint32_t n, uint8_t* __restrict__ root,
+    const uint8_t* __restrict__ slots, uint64_t slots_sq) {
+    const uint64_t sq = blockIdx.x;
+    uint32_t* src = lv + sq * lv_sq;
+    root += sq * 32;
+    if constexpr (kFromSlots) {
+        const uint8_t* in = slots + sq * slots_sq;
+        for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+            uint32_t I[kSlotWords], D[8];
+            load_slot_be(in + (uint64_t)i * kSlot, I);
+            rfc_leaf_u<false>(I, D, false);
+#pragma unroll
+            for (int j = 0; j < 8; j++) src[8 * i + j] = D[j];
+        }
+        __syncthreads();
+    }
     for (uint32_t m = n / 2; m >= 1; m >>= 1) {
         uint32_t* dst = src + 2 * m * 8;
         for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) {
@@ -93,10 +114,19 @@ __global__ __launch_bounds__(256) void gather_kernel(const GatherPiece* __restri
 
 }  // namespace
 
+hipError_t launch_rfc_levels_set(const uint8_t* root_slots, uint64_t slots_sq, uint32_t n_items, uint32_t n_squares,
+                                 uint32_t* rfc, uint64_t rfc_sq_words, uint8_t* data_roots, hipStream_t s) {
+    hipLaunchKernelGGL(rfc_levels_kernel<true>, dim3(n_squares), dim3(256), 0, s, rfc, rfc_sq_words, n_items,
+                       data_roots, root_slots, slots_sq);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------
 // ResidentSquare
 // ---------------------------------------------------------------------------
 ResidentSquare::~ResidentSquare() {
+    if (borrowed)   // the set's arenas outlive the member: only the per-call buffers are its own
+        for (DevBuf* b : {&eds, &levels, &col_levels, &roots_slots, &rfc, &rows, &cols, &root, &err}) *b = DevBuf{};
     for (DevBuf* b : {&eds, &levels, &col_levels, &roots_slots, &rfc, &rows, &cols, &root, &err, &scratch, &pieces})
         b->release();
 }
@@ -154,8 +184,8 @@ int Engine::square_create(const uint8_t* ods, uint32_t k, ResidentSquare* sq) {
     }
     // data root with every RFC-6962 level kept: leaf digests, then one workgroup
     CDA_TRY(check(launch_rfc_leaves(sq->roots_slots.as<uint8_t>(), 2 * W, sq->rfc.as<uint32_t>(), s), "rfc leaves"));
-    hipLaunchKernelGGL(rfc_levels_kernel, dim3(1), dim3(1024), 0, s, sq->rfc.as<uint32_t>(), 2 * W,
-                       sq->root.as<uint8_t>());
+    hipLaunchKernelGGL(rfc_levels_kernel<false>, dim3(1), dim3(1024), 0, s, sq->rfc.as<uint32_t>(), uint64_t{0}, 2 * W,
+                       sq->root.as<uint8_t>(), static_cast<const uint8_t*>(nullptr), uint64_t{0});
     CDA_TRY(launched("rfc levels"));
     CDA_TRY(read_push_order(sq->err.ptr, 1, &sq->push_err, s));
     return push_order_error(&sq->push_err, 1, ods, k, false);

@@ -31,6 +31,11 @@
 // copies back are out_regions.h's.
 // Every index the kernel uses was validated on the host
 // (Engine::square_sample_proofs).
+//
+// Sets.  The same kernel with a square index per sample serves a set of
+// resident squares (square_set.hip) in one launch: sample_kernel<true> takes
+// the arenas' bases and per-square strides and derives each wave's view from
+// them (Engine::square_set_sample_proofs).
 #include <cstring>
 #include <string>
 #include <vector>
@@ -51,7 +56,7 @@ constexpr uint32_t kSampleSlots = kProofMaxD + 2;   // proof nodes, the axis roo
 
 struct SampleArgs {
     ResidentView sq;
-    const uint32_t* coords;     // n words: row | col << 12 | axis << 24
+    const uint32_t* coords;     // n words: row | col << 12 | axis << 24 (a set: n pairs, the square second)
     uint32_t n;
     uint8_t* shares;            // any output may be NULL
     uint8_t* namespaces;
@@ -61,16 +66,13 @@ struct SampleArgs {
     uint8_t* aunts;
 };
 
-__global__ __launch_bounds__(64 * kSampleWaves) void sample_kernel(const SampleArgs a) {
-    __shared__ uint4 stage[kSampleWaves][stage_row(kSampleSlots)];
-    const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
-    const uint32_t i = blockIdx.x * kSampleWaves + wave;
-    const bool live = i < a.n;   // uniform over the wave; no early return: the workgroup meets at the barrier
-    const ResidentView& v = a.sq;
+// One wave's sample i of the square `v` (live: i is a sample of the batch; uniform over the wave, and no early
+// return before the barrier the workgroup meets at).  c: row | col << 12 | axis << 24.
+__device__ __forceinline__ void sample_wave(const ResidentView& v, const SampleArgs& a, uint32_t i, bool live,
+                                            uint32_t c, uint4* st, uint32_t lane) {
     const uint32_t W = 2 * v.k, D = v.log_w, A = D + 1;
     uint32_t row = 0, col = 0, axis = 0;
     if (live) {
-        const uint32_t c = a.coords[i];
         row = c & 0xFFFu;
         col = (c >> 12) & 0xFFFu;
         axis = c >> 24;
@@ -78,7 +80,6 @@ __global__ __launch_bounds__(64 * kSampleWaves) void sample_kernel(const SampleA
     const uint32_t p = axis ? row : col;      // leaf position in the axis tree
     const uint32_t tree = axis ? col : row;   // which tree of the axis
     const uint64_t cell = (uint64_t)row * W + col;
-    uint4* st = stage[wave];
     if (live) {
         // the share: 32 lanes x 16 bytes; its first two words also give the Q0 namespace
         uint4 sh = make_uint4(0, 0, 0, 0);
@@ -110,6 +111,33 @@ __global__ __launch_bounds__(64 * kSampleWaves) void sample_kernel(const SampleA
     if (a.nodes) store_packed<kNode>(sb, D, a.nodes + (uint64_t)i * D * kNode, lane);
     if (a.roots) store_packed<kNode>(sb + D * kSlot, 1, a.roots + (uint64_t)i * kNode, lane);
     if (a.namespaces) store_packed<kNs>(sb + (D + 1) * kSlot, 1, a.namespaces + (uint64_t)i * kNs, lane);
+}
+
+// Per-square strides of a set's arenas (square_set.hip), bytes; unused for a single square.
+struct SetStrides {
+    uint64_t eds, levels, col_levels, root_slots, rfc;
+};
+
+// kSet = false: the samples of the square a.sq.  kSet = true: samples across a set of resident squares --
+// a.sq holds the arenas' bases, sample i names its square in word 2i + 1 of the requests (word 2i: the
+// coordinates) and the wave reads that square's strides of the arenas.
+template <bool kSet>
+__global__ __launch_bounds__(64 * kSampleWaves) void sample_kernel(const SampleArgs a, const SetStrides sq) {
+    __shared__ uint4 stage[kSampleWaves][stage_row(kSampleSlots)];
+    const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+    const uint32_t i = blockIdx.x * kSampleWaves + wave;
+    const bool live = i < a.n;   // uniform over the wave
+    if constexpr (kSet) {
+        const uint2 req = live ? reinterpret_cast<const uint2*>(a.coords)[i] : make_uint2(0u, 0u);
+        const uint64_t y = req.y;   // validated on the host: below the set's square count
+        const ResidentView v{a.sq.eds + y * sq.eds, a.sq.levels + y * sq.levels,
+                             a.sq.col_levels + y * sq.col_levels, a.sq.root_slots + y * sq.root_slots,
+                             reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(a.sq.rfc) + y * sq.rfc),
+                             a.sq.k, a.sq.log_w};
+        sample_wave(v, a, i, live, req.x, stage[wave], lane);
+    } else {
+        sample_wave(a.sq, a, i, live, live ? a.coords[i] : 0u, stage[wave], lane);
+    }
 }
 
 // The first bad coordinate of a batch ("" if none): the text names the sample and the field.
@@ -147,8 +175,46 @@ int Engine::square_sample_proofs(ResidentSquare* sq, const uint32_t* rows, const
     CDA_TRY(h2d(scr, packed.data(), (size_t)n * 4, s, "H2D samples"));
     const SampleArgs a{sq->view(), reinterpret_cast<const uint32_t*>(scr), n, r_sh.dev(scr), r_ns.dev(scr),
                        r_nd.dev(scr), r_rt.dev(scr), r_lh.dev(scr), r_au.dev(scr)};
-    hipLaunchKernelGGL(sample_kernel, dim3((n + kSampleWaves - 1) / kSampleWaves), dim3(64 * kSampleWaves), 0, s, a);
+    hipLaunchKernelGGL(sample_kernel<false>, dim3((n + kSampleWaves - 1) / kSampleWaves), dim3(64 * kSampleWaves), 0, s,
+                       a, SetStrides{});
     CDA_TRY(launched("sample proofs"));
+    // `packed` is pageable and the outputs are the caller's: complete before returning
+    return regions_out(out, scr, false, s, "D2H samples");
+}
+
+int Engine::square_set_sample_proofs(ResidentSquareSet* set, const uint32_t* squares, const uint32_t* rows,
+                                     const uint32_t* cols, const uint8_t* axes, uint32_t n, const SampleOut& o) {
+    if (n == 0) return CDA_OK;
+    if (!squares || !rows || !cols) return fail(CDA_ERR_INVALID, "null buffer");
+    const uint32_t k = set->k, W = 2 * k, D = set->log_w, A = D + 1;
+    for (uint32_t i = 0; i < n; i++)
+        if (squares[i] >= set->n)
+            return fail(CDA_ERR_INVALID, "sample " + std::to_string(i) + ": square " + std::to_string(squares[i]) +
+                                             " is not below the set's " + std::to_string(set->n) + " squares");
+    const std::string bad = check_coords(rows, cols, axes, n, W);
+    if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
+    std::vector<uint32_t> packed((size_t)2 * n);
+    for (uint32_t i = 0; i < n; i++) {
+        packed[2 * i] = rows[i] | (cols[i] << 12) | ((axes ? axes[i] : 0u) << 24);
+        packed[2 * i + 1] = squares[i];
+    }
+    // scratch: the packed requests, then one struct-of-arrays region per requested output
+    OutRegions out((size_t)n * 8);
+    const auto r_sh = out.add(o.shares, (size_t)n * kShare), r_ns = out.add(o.namespaces, (size_t)n * kNs),
+               r_nd = out.add(o.nmt_nodes, (size_t)n * D * kNode), r_rt = out.add(o.axis_roots, (size_t)n * kNode),
+               r_lh = out.add(o.leaf_hash, (size_t)n * 32), r_au = out.add(o.aunts, (size_t)n * A * 32);
+    hipStream_t s = stream_;
+    CDA_TRY(ensure(set->scratch, out.total(), "hipMalloc"));
+    uint8_t* scr = set->scratch.as<uint8_t>();
+    CDA_TRY(h2d(scr, packed.data(), (size_t)n * 8, s, "H2D samples"));
+    const ResidentView base{set->eds.as<uint8_t>(), set->levels.as<uint8_t>(), set->col_levels.as<uint8_t>(),
+                            set->roots_slots.as<uint8_t>(), set->rfc.as<uint32_t>(), k, D};
+    const SampleArgs a{base, reinterpret_cast<const uint32_t*>(scr), n, r_sh.dev(scr), r_ns.dev(scr),
+                       r_nd.dev(scr), r_rt.dev(scr), r_lh.dev(scr), r_au.dev(scr)};
+    const SetStrides st{set->eds_sq, set->levels_sq, set->col_levels_sq, set->roots_slots_sq, set->rfc_sq};
+    hipLaunchKernelGGL(sample_kernel<true>, dim3((n + kSampleWaves - 1) / kSampleWaves), dim3(64 * kSampleWaves), 0, s,
+                       a, st);
+    CDA_TRY(launched("sample proofs of a set"));
     // `packed` is pageable and the outputs are the caller's: complete before returning
     return regions_out(out, scr, false, s, "D2H samples");
 }

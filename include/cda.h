@@ -533,6 +533,58 @@ int cda_sample_proofs_verify(cda_ctx *ctx, uint32_t k, uint32_t n, const uint8_t
                              const uint8_t *shares, const uint8_t *nmt_nodes, const uint8_t *axis_roots,
                              const uint8_t *leaf_hash, const uint8_t *aunts, uint8_t *verdict);
 
+/* ---- Sets of resident squares: built from a batch, sampled across ----------------
+ * What cda_square_create keeps for one square, built for n squares of one ODS width k in ONE submission
+ * (no per-square launch or copy), from a batch that lies on the host or is already in HBM: the output
+ * of cda_extend_dah_device / _inplace_device, a replayed batch, the squares cda_repair_batch_device
+ * repaired.  src / device_src holds
+ *   CDA_SET_FROM_ODS  n*k*k*512 bytes: every square is extended, then hashed;
+ *   CDA_SET_FROM_EDS  n*(2k)^2*512 bytes: the squares are copied and hashed as they are.  NO Reed-Solomon
+ *                     work is done and the parity is NOT checked: the roots commit to the bytes given,
+ *                     as NewDataAvailabilityHeader(eds) and cda_dah_from_eds do.  A caller that does not
+ *                     trust the source compares cda_square_set_dah's data roots with the ones it trusts.
+ * The set owns one arena per part (EDS, row and column tree levels, root slots, RFC-6962 levels, packed
+ * roots, data roots, push-order words), square i at base + i * stride with 64-bit offsets, so a set may be
+ * larger than 4 GiB per arena; it costs about 1.6 x the EDS bytes of HBM, plus the leaf staging
+ * (n*(2k)^2*96) and, for a host ODS source, the uploaded batch while it is built.
+ * Push order is per square: an unordered square stays in the set with its blind roots, its status is
+ * CDA_ERR_PUSH_ORDER, the create call returns CDA_ERR_PUSH_ORDER (text and cda_push_order_detail: the first
+ * such square) and STILL returns the set, as cda_square_create does; cda_push_order_detail_at(ctx, i, ...)
+ * names square i's first violation until the next device batch on the context.
+ * Both calls return when the set is complete.  The device variant orders its work after `stream` (NULL:
+ * the null stream) and waits for its own work only; device_src is read only, 16-byte aligned, and may be
+ * released on return.  CDA_ERR_INVALID, *out = NULL and nothing allocated: n == 0 or n >
+ * CDA_SET_MAX_SQUARES, k not a power of two <= 1024, an unknown kind, a NULL pointer. */
+#define CDA_SET_FROM_ODS 0
+#define CDA_SET_FROM_EDS 1
+#define CDA_SET_MAX_SQUARES 65535
+typedef struct cda_square_set cda_square_set;
+int cda_square_set_create(cda_ctx *ctx, const uint8_t *src, int kind, uint32_t k, uint32_t n, cda_square_set **out);
+int cda_square_set_create_device(cda_ctx *ctx, const void *device_src, int kind, uint32_t k, uint32_t n, void *stream,
+                                 cda_square_set **out);
+/* Ends the set and its members (handles from cda_square_set_at are dead afterwards). */
+int cda_square_set_destroy(cda_square_set *set);
+int cda_square_set_info(cda_square_set *set, uint32_t *k, uint32_t *n);   /* either may be NULL */
+/* Square i of the set as a cda_square, BORROWED: its buffers are views into the set's arenas (only the
+ * per-call scratch is its own), every cda_square_* call works on it, it lives as long as the set, and
+ * cda_square_destroy on it is CDA_ERR_INVALID and leaves set and member intact.  i >= n: CDA_ERR_INVALID. */
+int cda_square_set_at(cda_square_set *set, uint32_t i, cda_square **member);
+/* Any output may be NULL: row_roots, col_roots n*2k*90 each (square by square), data_roots n*32,
+ * status n (CDA_OK / CDA_ERR_PUSH_ORDER).  Host buffers, complete on return. */
+int cda_square_set_dah(cda_square_set *set, uint8_t *row_roots, uint8_t *col_roots, uint8_t *data_roots,
+                       int32_t *status);
+/* cda_square_sample_proofs across the set: sample i is cell (rows[i], cols[i]) of member squares[i] on axis
+ * axes[i] (NULL: all rows).  All members share k, so D, A, the six outputs and their strides are those of
+ * cda_square_sample_proofs and cda_sample_proofs_verify takes the arrays as they are (with each sample's
+ * own data root).  One launch, one upload of the requests and one copy back per requested output, whatever
+ * n and however many squares are named.  Validated on the host before anything is enqueued:
+ * CDA_ERR_INVALID naming the sample and the field (square, row, col or axis), outputs untouched.
+ * n == 0 returns CDA_OK. */
+int cda_square_set_sample_proofs(cda_square_set *set, const uint32_t *squares, const uint32_t *rows,
+                                 const uint32_t *cols, const uint8_t *axes, uint32_t n, uint8_t *shares,
+                                 uint8_t *namespaces, uint8_t *nmt_nodes, uint8_t *axis_roots, uint8_t *leaf_hash,
+                                 uint8_t *aunts);
+
 /* ---- Share-inclusion proofs of many ranges in one launch -----------------------
  * proof.NewShareInclusionProofFromEDS (pkg/proof/proof.go:77-145) for n ranges [starts[i], ends[i]) of
  * the ODS of one resident square at once, in the flat layout of cda_share_proof_batch below: the
