@@ -77,6 +77,8 @@ EXPORTED = (
     "cda_shares_parse_plan", "cda_shares_parse", "cda_square_parse_plan", "cda_square_parse",
     "cda_square_set_create", "cda_square_set_create_device", "cda_square_set_destroy", "cda_square_set_info",
     "cda_square_set_at", "cda_square_set_dah", "cda_square_set_sample_proofs",
+    "cda_square_set_namespace_plan", "cda_square_set_namespace_proofs", "cda_namespace_proofs_verify_set",
+    "cda_square_set_share_proofs",
 )
 # cda_square_set_create source kinds (include/cda.h)
 CDA_SET_FROM_ODS = 0
@@ -356,6 +358,11 @@ def load(path: str | None = None):
         L.cda_square_set_dah.argtypes = [vp, u8p, u8p, u8p, i32p]
         L.cda_square_set_sample_proofs.argtypes = [vp, u32p, u32p, u32p, u8p, C.c_uint32, u8p, u8p, u8p, u8p, u8p,
                                                    u8p]
+        L.cda_square_set_namespace_plan.argtypes = [vp, u32p, u8p, C.c_uint32, C.POINTER(NamespacePlanT)]
+        L.cda_square_set_namespace_proofs.argtypes = [vp, u32p, u8p, C.c_uint32, C.POINTER(NamespaceProofsOut)]
+        L.cda_namespace_proofs_verify_set.argtypes = [ctxp, C.c_uint32, u8p, C.c_uint32, u32p,
+                                                      C.POINTER(NamespaceProofBatch), u8p]
+        L.cda_square_set_share_proofs.argtypes = [vp, u32p, u32p, u32p, C.c_uint32, C.POINTER(ShareProofsOut)]
         L.cda_comm_unique_id.argtypes = [u8p]
         L.cda_comm_init.argtypes = [ctxp, C.c_int, C.c_int, u8p]
         L.cda_comm_destroy.argtypes = [ctxp]

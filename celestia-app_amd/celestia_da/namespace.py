@@ -8,6 +8,14 @@ data in a block and checks the answer against the DataAvailabilityHeader alone.
     answer = get_shares_by_namespace(ods, ns)                  # [(row, NMTProof, shares)]
     verify_namespaced_shares(row_roots, ns, answer) == 0
 
+and the same over a range of heights, a proof.ResidentSquareSet, in the launches
+of one square's call:
+
+    got = sqset.namespace_proofs([(square, ns), ...])          # cda_square_set_namespace_plan + _proofs
+    verdicts = got.verify(sqset.dah()[0])                      # cda_namespace_proofs_verify_set
+    answers = get_shares_by_namespace_set(sqset, ns)           # one answer per member
+    verify_namespaced_shares_set(row_roots, squares, ns, answers)
+
 Reference: nmt v0.22.0 NamespacedMerkleTree.ProveNamespace (an inclusion proof
 of the whole run of the namespace in a row, or an absence proof: the proof of
 the first leaf above it, carried as NMTProof.leaf_hash) and
@@ -181,6 +189,109 @@ def namespace_proofs(sq, namespaces, out: NamespaceProofsBatch | None = None) ->
     o = out.out_struct()
     sq.ctx.check(sq.ctx.lib.cda_square_namespace_proofs(sq.h, ptr(ns), len(ns), C.byref(o)))
     return out
+
+
+# ------------------------------------------------- the same across a set of squares
+def split_set_queries(queries):
+    """(squares, namespaces) as (n,) uint32 and (n, 29) uint8 arrays from rows
+    of (square, namespace): an iterable of (int, 29 bytes) pairs, or an (n, 30)
+    integer array whose first column is the square."""
+    if isinstance(queries, np.ndarray):
+        q = np.asarray(queries, dtype=np.int64).reshape(-1, 1 + NAMESPACE_SIZE)
+        sq, ns = q[:, 0], np.ascontiguousarray(q[:, 1:], dtype=np.uint8)
+    else:
+        rows = list(queries)
+        sq = np.array([int(s) for s, _ in rows], dtype=np.int64)
+        ns = _namespaces_array([x for _, x in rows])
+    bad = np.nonzero((sq < 0) | (sq >= 1 << 32))[0]
+    if bad.size:
+        raise _lib.CdaError(_lib.CDA_ERR_INVALID, f"query {bad[0]}: square {sq[bad[0]]} out of range")
+    return np.ascontiguousarray(sq, dtype=np.uint32), ns
+
+
+def _u32p(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def namespace_plan_set(sqset, queries) -> dict:
+    """cda_square_set_namespace_plan: the sizes of the answer to `queries`,
+    rows of (square, namespace), from a proof.ResidentSquareSet."""
+    return _plan_set(sqset, *split_set_queries(queries))
+
+
+def _plan_set(sqset, squares: np.ndarray, ns: np.ndarray) -> dict:
+    p = _lib.NamespacePlanT()
+    sqset.ctx.check(sqset.ctx.lib.cda_square_set_namespace_plan(sqset.h, _u32p(squares), ptr(ns), len(ns), C.byref(p)))
+    return {n: getattr(p, n) for n, _ in _lib.NamespacePlanT._fields_}
+
+
+class SetNamespaceProofs:
+    """The answer to namespace queries across a proof.ResidentSquareSet
+    (cda_square_set_namespace_proofs): ONE flat NamespaceProofsBatch in request
+    order and the square each query names."""
+
+    def __init__(self, batch: NamespaceProofsBatch, squares):
+        self.batch, self.squares = batch, np.ascontiguousarray(squares, dtype=np.uint32)
+
+    def __len__(self) -> int:
+        return len(self.batch)
+
+    def answers(self) -> list:
+        """One answer per query, as NamespaceProofsBatch.answers()."""
+        return self.batch.answers()
+
+    def verify(self, row_roots, ctx=None) -> np.ndarray:
+        """cda_namespace_proofs_verify_set: query q against the DAH squares[q]
+        of `row_roots`, the (n_squares, 2k, 90) array of ResidentSquareSet.dah()
+        or of trusted DAHs.  Verdicts as NamespaceProofsBatch.verify."""
+        ctx = ctx or default_context()
+        roots = np.ascontiguousarray(row_roots, dtype=np.uint8).reshape(-1)
+        per_dah = 2 * self.batch.k * NMT_ROOT_SIZE
+        if roots.size % per_dah:
+            raise ValueError(f"{roots.size} bytes of row roots are no whole number of DAHs of {per_dah}")
+        verdict = np.full(max(1, len(self)), 255, dtype=np.uint8)
+        b = self.batch.batch()
+        ctx.check(ctx.lib.cda_namespace_proofs_verify_set(ctx.h, self.batch.k, ptr(roots), roots.size // per_dah,
+                                                          _u32p(self.squares), C.byref(b), ptr(verdict)))
+        return verdict[:len(self)]
+
+
+def namespace_proofs_set(sqset, queries, out: NamespaceProofsBatch | None = None) -> SetNamespaceProofs:
+    """cda_square_set_namespace_plan, then cda_square_set_namespace_proofs into
+    buffers of the plan's sizes (or into `out`, a NamespaceProofsBatch.empty):
+    the queries -- rows of (square, namespace) -- of any number of members in
+    the launches of one square's call."""
+    squares, ns = split_set_queries(queries)
+    if out is None:
+        out = NamespaceProofsBatch.empty(sqset.k, ns, _plan_set(sqset, squares, ns))
+    o = out.out_struct()
+    sqset.ctx.check(sqset.ctx.lib.cda_square_set_namespace_proofs(sqset.h, _u32p(squares), ptr(ns), len(ns),
+                                                                  C.byref(o)))
+    return SetNamespaceProofs(out, squares)
+
+
+def get_shares_by_namespace_set(sqset, namespace: bytes, squares=None) -> list:
+    """GetSharesByNamespace over a range of heights in one call: one answer
+    (as get_shares_by_namespace) per member named in `squares`, by default all
+    of them."""
+    squares = list(range(len(sqset))) if squares is None else [int(s) for s in squares]
+    return namespace_proofs_set(sqset, [(s, namespace) for s in squares]).answers()
+
+
+def verify_namespaced_shares_set(row_roots, squares, namespaces, answers, ctx=None) -> np.ndarray:
+    """The verdicts of cda_namespace_proofs_verify_set for answers of
+    get_shares_by_namespace_set: answer q is of `namespaces[q]` (one namespace
+    for all: 29 bytes) and is checked against the DAH squares[q] of `row_roots`,
+    (n_squares, 2k, 90).  0 means that these are all the shares of the
+    namespace in that square."""
+    roots = np.ascontiguousarray(row_roots, dtype=np.uint8)
+    if roots.ndim != 3 or roots.shape[2] != NMT_ROOT_SIZE:
+        raise ValueError("row_roots must have the shape (n_squares, 2k, 90)")
+    k = roots.shape[1] // 2
+    if isinstance(namespaces, (bytes, bytearray)):
+        namespaces = [bytes(namespaces)] * len(answers)
+    batch = NamespaceProofsBatch.from_answers(k, namespaces, answers)
+    return SetNamespaceProofs(batch, np.asarray(squares, dtype=np.uint32)).verify(roots, ctx)
 
 
 def get_shares_by_namespace(ods_or_square, namespace: bytes, ctx=None) -> list:

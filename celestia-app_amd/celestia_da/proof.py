@@ -446,6 +446,41 @@ class ResidentSquareSet:
         from . import sampling
         return sampling.sample_proofs_set(self, coords, out)
 
+    def namespace_plan(self, queries) -> dict:
+        """cda_square_set_namespace_plan: the sizes of the answer to `queries`,
+        rows of (square, 29-byte namespace)."""
+        from . import namespace
+        return namespace.namespace_plan_set(self, queries)
+
+    def namespace_proofs(self, queries, out=None):
+        """ResidentSquare.namespace_proofs across the set
+        (cda_square_set_namespace_proofs): `queries` are rows of (square,
+        namespace) of any number of members, answered in the launches of one
+        square's call.  Returns a namespace.SetNamespaceProofs: the flat
+        NamespaceProofsBatch in request order plus the squares column."""
+        from . import namespace
+        return namespace.namespace_proofs_set(self, queries, out)
+
+    def share_proofs_batch(self, ranges, out=None) -> "SetShareProofs":
+        """ResidentSquare.share_proofs_batch across the set
+        (cda_square_set_share_proofs, one launch): `ranges` are rows of
+        (square, start, end).  out: a ShareProofsBatch.empty(k, ranges[:, 1:])
+        to fill instead of a new one."""
+        r = np.asarray(ranges, dtype=np.int64).reshape(-1, 3)
+        if r.size and (r[:, 0].min() < 0 or r[:, 0].max() >= 1 << 32):
+            raise _lib.CdaError(_lib.CDA_ERR_INVALID, "square out of range")
+        rr = _ranges_array(r[:, 1:])
+        if out is None:
+            out = ShareProofsBatch.empty(self.k, rr)
+        squares = np.ascontiguousarray(r[:, 0], dtype=np.uint32)
+        starts, ends = np.ascontiguousarray(rr[:, 0]), np.ascontiguousarray(rr[:, 1])
+        u32p = C.POINTER(C.c_uint32)
+        o = out.out_struct()
+        self.ctx.check(self.ctx.lib.cda_square_set_share_proofs(self.h, squares.ctypes.data_as(u32p),
+                                                                starts.ctypes.data_as(u32p),
+                                                                ends.ctypes.data_as(u32p), len(rr), C.byref(o)))
+        return SetShareProofs(out, squares)
+
     def close(self):
         """Ends the set and its members: a ResidentSquare taken from it is closed too."""
         if getattr(self, "h", None):
@@ -598,6 +633,34 @@ class ShareProofsBatch:
                                   row_proof=RowProof(cut(rb, segs.start, segs.stop, NMT_ROOT_SIZE), rp, r0[i], r1[i]),
                                   namespace_version=ns[0]))
         return out
+
+
+class SetShareProofs:
+    """The share proofs of ranges across a ResidentSquareSet
+    (cda_square_set_share_proofs): ONE flat ShareProofsBatch in request order
+    and the square each range names."""
+
+    def __init__(self, batch: ShareProofsBatch, squares):
+        self.batch, self.squares = batch, np.ascontiguousarray(squares, dtype=np.uint32)
+
+    def __len__(self):
+        return len(self.batch)
+
+    def data_roots(self, set_roots) -> np.ndarray:
+        """One data root per proof, (n, 32), from the set's (n_squares, 32) data roots."""
+        return np.ascontiguousarray(np.asarray(set_roots, dtype=np.uint8).reshape(-1, 32)[self.squares])
+
+    def verify(self, data_roots, ctx=None) -> np.ndarray:
+        """cda_share_proofs_verify of the batch, proof i against the data root
+        of its square: data_roots is the set's (n_squares, 32) array
+        (ResidentSquareSet.dah()[2]) or trusted roots of the same shape."""
+        if len(self) == 0:
+            return np.zeros(0, dtype=np.uint8)
+        return self.batch.verify(self.data_roots(data_roots), ctx)
+
+    def proofs(self, namespaces=None) -> list:
+        """One ShareProof per range, as ShareProofsBatch.proofs."""
+        return self.batch.proofs(namespaces)
 
 
 # ------------------------------------------------- blob inclusion by share commitment

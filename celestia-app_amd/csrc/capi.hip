@@ -713,6 +713,33 @@ int cda_square_set_sample_proofs(cda_square_set* set, const uint32_t* squares, c
     });
 }
 
+int cda_square_set_namespace_plan(cda_square_set* set, const uint32_t* squares, const uint8_t* namespaces, uint32_t n,
+                                  cda_namespace_plan_t* out) {
+    if (!set) return CDA_ERR_INVALID;
+    return guarded(set->ctx, [&](cda::Engine& e) -> int {
+        if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.square_set_namespace_plan(&set->set, squares, namespaces, n, out);
+    });
+}
+
+int cda_square_set_namespace_proofs(cda_square_set* set, const uint32_t* squares, const uint8_t* namespaces,
+                                    uint32_t n, const cda_namespace_proofs_out* out) {
+    if (!set) return CDA_ERR_INVALID;
+    return guarded(set->ctx, [&](cda::Engine& e) -> int {
+        if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.square_set_namespace_proofs(&set->set, squares, namespaces, n, *out);
+    });
+}
+
+int cda_square_set_share_proofs(cda_square_set* set, const uint32_t* squares, const uint32_t* starts,
+                                const uint32_t* ends, uint32_t n, const cda_share_proofs_out* out) {
+    if (!set) return CDA_ERR_INVALID;
+    return guarded(set->ctx, [&](cda::Engine& e) -> int {
+        if (!out) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.square_set_share_proofs(&set->set, squares, starts, ends, n, *out);
+    });
+}
+
 int cda_square_share_proofs_plan(uint32_t k, const uint32_t* starts, const uint32_t* ends, uint32_t n,
                                  cda_share_proofs_plan_t* out) {
     // Host-only (no device work), no context.
@@ -826,6 +853,14 @@ int cda_square_parse(cda_square* sq, const uint32_t* starts, const uint32_t* end
 int cda_namespace_proofs_verify(cda_ctx* ctx, uint32_t k, const uint8_t* row_roots,
                                 const cda_namespace_proof_batch* b, uint8_t* verdict) {
     return guarded(ctx, [&](cda::Engine& e) -> int { return e.namespace_proofs_verify(k, row_roots, b, verdict); });
+}
+
+int cda_namespace_proofs_verify_set(cda_ctx* ctx, uint32_t k, const uint8_t* row_roots, uint32_t n_squares,
+                                    const uint32_t* squares, const cda_namespace_proof_batch* b, uint8_t* verdict) {
+    return guarded(ctx, [&](cda::Engine& e) -> int {
+        if (b && b->n_queries && !squares) return e.fail(CDA_ERR_INVALID, "null squares");
+        return e.namespace_proofs_verify_set(k, row_roots, n_squares, squares, b, verdict);
+    });
 }
 
 int cda_sample_proofs_verify(cda_ctx* ctx, uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,

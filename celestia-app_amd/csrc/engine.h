@@ -343,9 +343,14 @@ class Engine {
     // row, nmt_count[i] of row i's valid.
     int square_share_proof(ResidentSquare* sq, uint32_t start, uint32_t end, const cda_share_proofs_out& out,
                            uint32_t* nmt_count);
+    // The body of both: the ranges of one square (sq), or of the members squares[i] of a set (sq == NULL).
+    int range_share_proofs(ResidentSquare* sq, ResidentSquareSet* set, const uint32_t* squares,
+                           const uint32_t* starts, const uint32_t* ends, uint32_t n, const cda_share_proofs_out& out,
+                           uint32_t* nmt_count, size_t one_copy_max);
     // What both producers of a segment table end in (share_proofs.hip): the table up, the proof kernel's one
-    // launch, the requested outputs back; complete on return.
-    int emit_segments(ResidentSquare* sq, const SegmentEmit& em);
+    // launch, the requested outputs back; complete on return.  A square, or a set (sq == NULL): its segments
+    // name their squares (segment_table.h seg_row_word) and the call uses the set's own scratch.
+    int emit_segments(ResidentSquare* sq, ResidentSquareSet* set, const SegmentEmit& em);
     // Blob commitment proofs of n blobs (start, share_len) in one launch of the same kernel (share_proofs.hip):
     // per row the subtree roots of commitment_proofs_plan.h's cover, the nodes and the row proof of the share
     // proofs; out.commitments costs one further launch (commit.hip).  A square whose push order failed answers
@@ -353,6 +358,7 @@ class Engine {
     int square_commitment_proofs(ResidentSquare* sq, const uint32_t* starts, const uint32_t* share_lens, uint32_t n,
                                  uint32_t threshold, const cda_commitment_proofs_out& out);
     int fail_unordered_square(const ResidentSquare* sq, const char* why);   // CDA_ERR_PUSH_ORDER, po_* set
+    int fail_unordered_square(uint32_t push_err, const std::string& who, const char* why);
     // All shares of n namespaces with nmt ProveNamespace's proofs, absence proofs included (namespace_proofs.hip):
     // one search launch whose (query, row) words come back, the host plan (namespace_proofs_plan.h), and for the
     // proofs emit_segments.  A square whose push order failed answers CDA_ERR_PUSH_ORDER.
@@ -361,6 +367,9 @@ class Engine {
     int square_namespace_plan(ResidentSquare* sq, const uint8_t* namespaces, uint32_t n, cda_namespace_plan_t* out);
     int square_namespace_proofs(ResidentSquare* sq, const uint8_t* namespaces, uint32_t n,
                                 const cda_namespace_proofs_out& out);
+    // The words of one square, or of the members squares[q] of a set (sq == NULL), to the table and the launch.
+    int namespace_segments(ResidentSquare* sq, ResidentSquareSet* set, const uint32_t* squares,
+                           const std::vector<uint32_t>& words, uint32_t n, const cda_namespace_proofs_out& out);
     // Shares of Q0 back into transactions and blobs (parse.hip): the headers of the ranges' shares come back
     // through the gather kernel, the host builds and checks the sequence table (parse_plan.h), one more gather
     // launch packs the raw bytes, the compact streams come back for the unit walk.  plan and out may be NULL.
@@ -377,6 +386,18 @@ class Engine {
     // square_sample_proofs across the set (sample.hip): sample i of member squares[i], one launch.
     int square_set_sample_proofs(ResidentSquareSet* set, const uint32_t* squares, const uint32_t* rows,
                                  const uint32_t* cols, const uint8_t* axes, uint32_t n, const SampleOut& out);
+    // The namespace and share-range queries across the set (namespace_proofs.hip, share_proofs.hip): query i
+    // is of member squares[i]; the launches are those of the single square's calls, whatever n and however many
+    // members are named, from the set instantiations of the search and the proof kernel.  A namespace query of
+    // a member whose push order failed answers CDA_ERR_PUSH_ORDER; share proofs of it are served.
+    int square_set_namespace_search(ResidentSquareSet* set, const uint32_t* squares, const uint8_t* namespaces,
+                                    uint32_t n, std::vector<uint32_t>* words);
+    int square_set_namespace_plan(ResidentSquareSet* set, const uint32_t* squares, const uint8_t* namespaces,
+                                  uint32_t n, cda_namespace_plan_t* out);
+    int square_set_namespace_proofs(ResidentSquareSet* set, const uint32_t* squares, const uint8_t* namespaces,
+                                    uint32_t n, const cda_namespace_proofs_out& out);
+    int square_set_share_proofs(ResidentSquareSet* set, const uint32_t* squares, const uint32_t* starts,
+                                const uint32_t* ends, uint32_t n, const cda_share_proofs_out& out);
     // The verifying side: the batch of share_proofs_verify built from the coordinates.
     int sample_proofs_verify(uint32_t k, uint32_t n, const uint8_t* data_roots, const uint32_t* rows,
                              const uint32_t* cols, const uint8_t* axes, const uint8_t* shares,
@@ -414,6 +435,10 @@ class Engine {
     // selection (verify.hip): verdict[q] = 0 valid, 1 rows, 2 hash or absence leaf, 3 incomplete.
     int namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const cda_namespace_proof_batch* b,
                                 uint8_t* verdict);
+    // The same against the DAHs of n_squares squares (row_roots: n_squares * 2k roots), query q against the DAH
+    // squares[q]; squares == NULL: one DAH, the call above.
+    int namespace_proofs_verify_set(uint32_t k, const uint8_t* row_roots, uint32_t n_squares, const uint32_t* squares,
+                                    const cda_namespace_proof_batch* b, uint8_t* verdict);
     // Blob commitment proofs (commitment_verify.hip): verdict[p] = 0 valid, 4 not one contiguous blob, 1 row
     // proof, 2 subtree roots and nodes do not rebuild the row root, 3 commitment.  Four launches, one
     // synchronisation.

@@ -20,6 +20,13 @@
 // per (query, row < k) (namespace_word: selected, equal, less), n * k * 4 bytes
 // in one copy back; rows >= k are never selected (their min is the parity
 // namespace, which no query may be).
+//
+// Sets.  The same two launches serve queries across a set of resident squares
+// (cda_square_set_namespace_plan / _proofs): query q names its member in
+// squares[q], namespace_search_kernel<true> reads that member's root slots and
+// leaf level from the arenas' bases and strides, the words stay [n][k], and
+// every segment of the table names its square beside its row (segment_table.h).
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -47,6 +54,7 @@ struct SearchArgs {
     const uint8_t* namespaces;   // [n][29]
     uint32_t n, row_blocks;
     uint32_t* words;             // [n][k]
+    const uint32_t* squares;     // a set: [n], the member each query is of
 };
 
 // A namespace as eight big-endian words (the last holds byte 28 in its top byte), from any address ...
@@ -75,17 +83,28 @@ __device__ __forceinline__ int cmp_ns(const uint32_t (&a)[8], const uint32_t (&b
     return c;
 }
 
-__global__ __launch_bounds__(64 * kSearchWaves) void namespace_search_kernel(const SearchArgs a) {
+// kSet = false: the queries of the square a.sq.  kSet = true: queries across a set of resident squares --
+// a.sq holds the arenas' bases, query q is of member a.squares[q] (validated on the host) and the wave reads
+// that member's strides of the root slots and the row levels.
+template <bool kSet>
+__global__ __launch_bounds__(64 * kSearchWaves) void namespace_search_kernel(const SearchArgs a, const SetStrides sq) {
     const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const uint32_t g = blockIdx.x * kSearchWaves + wave;
     if (g >= a.n * a.row_blocks) return;   // uniform over the wave; the kernel has no barrier
     const uint32_t k = a.sq.k, W = 2 * k;
     const uint32_t q = g / a.row_blocks, row0 = (g % a.row_blocks) * 64, r = row0 + lane;
+    const uint8_t* root_slots = a.sq.root_slots;
+    const uint8_t* levels = a.sq.levels;
+    if constexpr (kSet) {
+        const uint64_t y = a.squares[q];
+        root_slots += y * sq.root_slots;
+        levels += y * sq.levels;
+    }
     uint32_t ns[8];
     load_ns_bytes(a.namespaces + (uint64_t)q * kNs, ns);
     bool selected = false;
     if (r < k) {
-        const uint8_t* root = a.sq.root_slots + (uint64_t)r * kSlot;
+        const uint8_t* root = root_slots + (uint64_t)r * kSlot;
         uint32_t mn[8], mx[8];
         load_ns_slot(root, mn);
         load_ns_bytes(root + kNs, mx);
@@ -96,7 +115,7 @@ __global__ __launch_bounds__(64 * kSearchWaves) void namespace_search_kernel(con
     while (rows) {
         const uint32_t rl = (uint32_t)__ffsll(rows) - 1;
         rows &= rows - 1;
-        const uint8_t* leaves = a.sq.levels + (uint64_t)(row0 + rl) * W * kSlot;
+        const uint8_t* leaves = levels + (uint64_t)(row0 + rl) * W * kSlot;
         uint32_t less = 0, equal = 0;
         for (uint32_t base = 0; base < k; base += 64) {
             const uint32_t j = base + lane;
@@ -118,11 +137,16 @@ __global__ __launch_bounds__(64 * kSearchWaves) void namespace_search_kernel(con
 
 // What the calls that need nmt's own trees answer for a square whose push order failed.
 int Engine::fail_unordered_square(const ResidentSquare* sq, const char* why) {
-    const push_order::Violation v = push_order::decode(sq->push_err);
+    return fail_unordered_square(sq->push_err, "", why);
+}
+
+// `who`: "" or what names the square among the call's requests, ending in ": ".
+int Engine::fail_unordered_square(uint32_t push_err, const std::string& who, const char* why) {
+    const push_order::Violation v = push_order::decode(push_err);
     po_axis = v.axis;
     po_index = v.index;
     po_pos = v.pos;
-    return fail(CDA_ERR_PUSH_ORDER, std::string("the square's ") + (v.axis == 0 ? "row " : "column ") +
+    return fail(CDA_ERR_PUSH_ORDER, who + "the square's " + (v.axis == 0 ? "row " : "column ") +
                                         std::to_string(v.index) + " is not ordered by namespace at position " +
                                         std::to_string(v.pos) + ": " + why);
 }
@@ -144,10 +168,56 @@ int Engine::square_namespace_search(ResidentSquare* sq, const uint8_t* namespace
     CDA_TRY(ensure(sq->scratch, ns_bytes + word_bytes, "hipMalloc"));
     uint8_t* scr = sq->scratch.as<uint8_t>();
     CDA_TRY(h2d(scr, namespaces, (size_t)n * kNs, s, "H2D namespaces"));
-    const SearchArgs a{sq->view(), scr, n, row_blocks, reinterpret_cast<uint32_t*>(scr + ns_bytes)};
-    hipLaunchKernelGGL(namespace_search_kernel, dim3((n * row_blocks + kSearchWaves - 1) / kSearchWaves),
-                       dim3(64 * kSearchWaves), 0, s, a);
+    const SearchArgs a{sq->view(), scr, n, row_blocks, reinterpret_cast<uint32_t*>(scr + ns_bytes), nullptr};
+    hipLaunchKernelGGL(namespace_search_kernel<false>, dim3((n * row_blocks + kSearchWaves - 1) / kSearchWaves),
+                       dim3(64 * kSearchWaves), 0, s, a, SetStrides{});
     CDA_TRY(launched("namespace search"));
+    CDA_TRY(d2h(words->data(), a.words, word_bytes, s, "D2H namespace search"));
+    return sync(s);
+}
+
+// Query q is (squares[q], namespaces + 29 q): one upload of the namespaces with the squares behind them, one
+// launch of the set instantiation over the arenas' bases, the n * k words back.
+int Engine::square_set_namespace_search(ResidentSquareSet* set, const uint32_t* squares, const uint8_t* namespaces,
+                                        uint32_t n, std::vector<uint32_t>* words) {
+    const uint32_t k = set->k;
+    if (n && !squares) return fail(CDA_ERR_INVALID, "null squares");
+    if (n && !namespaces) return fail(CDA_ERR_INVALID, "null buffer");   // the single square's text
+    for (uint32_t q = 0; q < n; q++)
+        if (squares[q] >= set->n)
+            return fail(CDA_ERR_INVALID, "query " + std::to_string(q) + ": square " + std::to_string(squares[q]) +
+                                             " is not below the set's " + std::to_string(set->n) + " squares");
+    const std::string bad = namespace_queries_check(k, namespaces, n);
+    if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
+    for (uint32_t q = 0; q < n; q++)
+        if (set->push_err[squares[q]] != push_order::kOrdered)
+            return fail_unordered_square(set->push_err[squares[q]],
+                                         "query " + std::to_string(q) + ": square " + std::to_string(squares[q]) + ": ",
+                                         "nmt builds no tree of it, so no namespace proof");
+    words->assign((size_t)n * k, 0);
+    if (n == 0) return CDA_OK;
+    const uint32_t row_blocks = (k + 63) / 64;
+    if ((uint64_t)n * row_blocks > (uint64_t)INT32_MAX)
+        return fail(CDA_ERR_INVALID, "too many queries for one launch");
+    // the upload: the namespaces, padded to a word, then the squares
+    const size_t ns_words = ((size_t)n * kNs + 3) / 4, up_bytes = OutRegions::align((ns_words + n) * 4),
+                 word_bytes = (size_t)n * k * 4;
+    std::vector<uint32_t> up(ns_words + n, 0);
+    std::memcpy(up.data(), namespaces, (size_t)n * kNs);
+    std::memcpy(up.data() + ns_words, squares, (size_t)n * 4);
+    hipStream_t s = stream_;
+    CDA_TRY(ensure(set->scratch, up_bytes + word_bytes, "hipMalloc"));
+    uint8_t* scr = set->scratch.as<uint8_t>();
+    CDA_TRY(h2d(scr, up.data(), up.size() * 4, s, "H2D namespace queries"));
+    const ResidentView base{set->eds.as<uint8_t>(), set->levels.as<uint8_t>(), set->col_levels.as<uint8_t>(),
+                            set->roots_slots.as<uint8_t>(), set->rfc.as<uint32_t>(), k, set->log_w};
+    const SearchArgs a{base, scr, n, row_blocks, reinterpret_cast<uint32_t*>(scr + up_bytes),
+                       reinterpret_cast<const uint32_t*>(scr) + ns_words};
+    const SetStrides st{set->eds_sq, set->levels_sq, set->col_levels_sq, set->roots_slots_sq, set->rfc_sq};
+    hipLaunchKernelGGL(namespace_search_kernel<true>, dim3((n * row_blocks + kSearchWaves - 1) / kSearchWaves),
+                       dim3(64 * kSearchWaves), 0, s, a, st);
+    CDA_TRY(launched("namespace search of a set"));
+    // `up` is pageable: complete before returning
     CDA_TRY(d2h(words->data(), a.words, word_bytes, s, "D2H namespace search"));
     return sync(s);
 }
@@ -163,14 +233,40 @@ int Engine::square_namespace_plan(ResidentSquare* sq, const uint8_t* namespaces,
     return CDA_OK;
 }
 
+int Engine::square_set_namespace_plan(ResidentSquareSet* set, const uint32_t* squares, const uint8_t* namespaces,
+                                      uint32_t n, cda_namespace_plan_t* out) {
+    std::vector<uint32_t> words;
+    CDA_TRY(square_set_namespace_search(set, squares, namespaces, n, &words));
+    NamespacePlan p;
+    const std::string bad = namespace_proofs_plan(set->k, words.data(), n, &p);
+    if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
+    *out = cda_namespace_plan_t{p.n_segments, p.n_nodes, p.n_shares};
+    return CDA_OK;
+}
+
 int Engine::square_namespace_proofs(ResidentSquare* sq, const uint8_t* namespaces, uint32_t n,
                                     const cda_namespace_proofs_out& o) {
-    const uint32_t D = sq->log_w;
-    std::vector<uint32_t> words, seg_off;
+    std::vector<uint32_t> words;
     CDA_TRY(square_namespace_search(sq, namespaces, n, &words));
+    return namespace_segments(sq, nullptr, nullptr, words, n, o);
+}
+
+int Engine::square_set_namespace_proofs(ResidentSquareSet* set, const uint32_t* squares, const uint8_t* namespaces,
+                                        uint32_t n, const cda_namespace_proofs_out& o) {
+    std::vector<uint32_t> words;
+    CDA_TRY(square_set_namespace_search(set, squares, namespaces, n, &words));
+    return namespace_segments(nullptr, set, squares, words, n, o);
+}
+
+// The host pass and the proof launch of both: the search's words of one square (sq), or of the members
+// squares[q] of a set, to the segment table; a set's segments name their squares beside their rows.
+int Engine::namespace_segments(ResidentSquare* sq, ResidentSquareSet* set, const uint32_t* squares,
+                               const std::vector<uint32_t>& words, uint32_t n, const cda_namespace_proofs_out& o) {
+    const uint32_t k = sq ? sq->k : set->k, D = sq ? sq->log_w : set->log_w;
+    std::vector<uint32_t> seg_off;
     NamespacePlan p;
     std::vector<NamespaceSegment> found;
-    const std::string bad = namespace_proofs_plan(sq->k, words.data(), n, &p, &found, &seg_off);
+    const std::string bad = namespace_proofs_plan(k, words.data(), n, &p, &found, &seg_off);
     if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
     const uint32_t S = (uint32_t)p.n_segments;
     if (o.seg_off)
@@ -186,7 +282,8 @@ int Engine::square_namespace_proofs(ResidentSquare* sq, const uint8_t* namespace
     for (uint32_t g = 0; g < S; g++) {
         const NamespaceSegment& sg = found[g];
         const bool absence = sg.kind == kNsAbsence;
-        segs[g] = SegEntry{sg.row, sg.s0 | (sg.e0 << 16) | (absence ? kSegAbsence : 0u), node_at, unit_at, share_at,
+        segs[g] = SegEntry{seg_row_word(sg.row, squares ? squares[sg.query] : 0u),
+                           sg.s0 | (sg.e0 << 16) | (absence ? kSegAbsence : 0u), node_at, unit_at, share_at,
                            sg.query, kNoFirstCell};
         if (o.row) o.row[g] = sg.row;
         if (o.kind) o.kind[g] = sg.kind;
@@ -205,7 +302,7 @@ int Engine::square_namespace_proofs(ResidentSquare* sq, const uint8_t* namespace
     em.nodes = o.nodes;
     em.shares = o.shares;
     em.absence_leaf = o.absence_leaf;
-    return emit_segments(sq, em);
+    return emit_segments(sq, set, em);
 }
 
 }  // namespace cda

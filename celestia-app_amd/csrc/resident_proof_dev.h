@@ -28,6 +28,20 @@ struct ResidentView {
     uint32_t k, log_w;
 };
 
+// Per-square strides of a set's arenas (square_set.hip), bytes; unused for a single square.
+struct SetStrides {
+    uint64_t eds, levels, col_levels, root_slots, rfc;
+};
+
+// The view of square y of a set: `base` holds the arenas' bases.  y was validated on the host (below the
+// set's square count); the offsets are 64-bit, an arena may be past 4 GiB.
+__device__ __forceinline__ ResidentView member_view(const ResidentView& base, const SetStrides& sq, uint64_t y) {
+    return ResidentView{base.eds + y * sq.eds, base.levels + y * sq.levels, base.col_levels + y * sq.col_levels,
+                        base.root_slots + y * sq.root_slots,
+                        reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(base.rfc) + y * sq.rfc),
+                        base.k, base.log_w};
+}
+
 // Lane `lane`'s share of staging `count` slots into the row `st`, six 16-byte
 // loads per slot: slot(n) gives the address of the n-th slot and the position
 // in the row it goes to.

@@ -113,11 +113,6 @@ __device__ __forceinline__ void sample_wave(const ResidentView& v, const SampleA
     if (a.namespaces) store_packed<kNs>(sb + (D + 1) * kSlot, 1, a.namespaces + (uint64_t)i * kNs, lane);
 }
 
-// Per-square strides of a set's arenas (square_set.hip), bytes; unused for a single square.
-struct SetStrides {
-    uint64_t eds, levels, col_levels, root_slots, rfc;
-};
-
 // kSet = false: the samples of the square a.sq.  kSet = true: samples across a set of resident squares --
 // a.sq holds the arenas' bases, sample i names its square in word 2i + 1 of the requests (word 2i: the
 // coordinates) and the wave reads that square's strides of the arenas.
@@ -129,12 +124,7 @@ __global__ __launch_bounds__(64 * kSampleWaves) void sample_kernel(const SampleA
     const bool live = i < a.n;   // uniform over the wave
     if constexpr (kSet) {
         const uint2 req = live ? reinterpret_cast<const uint2*>(a.coords)[i] : make_uint2(0u, 0u);
-        const uint64_t y = req.y;   // validated on the host: below the set's square count
-        const ResidentView v{a.sq.eds + y * sq.eds, a.sq.levels + y * sq.levels,
-                             a.sq.col_levels + y * sq.col_levels, a.sq.root_slots + y * sq.root_slots,
-                             reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(a.sq.rfc) + y * sq.rfc),
-                             a.sq.k, a.sq.log_w};
-        sample_wave(v, a, i, live, req.x, stage[wave], lane);
+        sample_wave(member_view(a.sq, sq, req.y), a, i, live, req.x, stage[wave], lane);
     } else {
         sample_wave(a.sq, a, i, live, live ? a.coords[i] : 0u, stage[wave], lane);
     }

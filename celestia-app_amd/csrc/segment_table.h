@@ -15,7 +15,7 @@ constexpr uint32_t kUnitShares = 16;   // shares one wave copies
 
 // One segment (one leaf range of one row tree), as uploaded: 32 bytes.
 struct SegEntry {
-    uint32_t row;
+    uint32_t row;          // seg_row_word: the row, and above it the square of a set (0 for a single square)
     uint32_t range;        // s0 | e0 << 16: the leaf range in the row tree; kSegAbsence: no shares, the leaf s0 itself
     uint32_t node_off;     // first node of the segment in `nodes`
     uint32_t unit_off;     // first share unit of the segment; kSegSubtree: log2 of the blob's subtree width
@@ -29,6 +29,14 @@ constexpr uint32_t kSegSubtree = 1u << 30;   // no shares: the subtree roots of 
 constexpr uint32_t kSegEndMask = 0xFFFu;   // e0 <= 2048
 constexpr uint32_t kNoFirstCell = 0xFFFFFFFFu;
 constexpr uint32_t kSegWords = sizeof(SegEntry) / 4;
+
+// The `row` word.  Rows are below 2048 (2k <= 2048) and a set holds at most 65 535 squares
+// (CDA_SET_MAX_SQUARES), so the square a segment is served from lies beside its row: the row in the low half,
+// the square in the high half.  A single square's table has square 0: its word is the row itself.
+constexpr uint32_t kSegRowBits = 16, kSegRowMask = (1u << kSegRowBits) - 1, kSegMaxSquares = 65535;
+constexpr uint32_t seg_row_word(uint32_t row, uint32_t square) { return row | (square << kSegRowBits); }
+constexpr uint32_t seg_row(uint32_t word) { return word & kSegRowMask; }
+constexpr uint32_t seg_square(uint32_t word) { return word >> kSegRowBits; }
 
 constexpr uint32_t seg_units(uint32_t shares) { return (shares + kUnitShares - 1) / kUnitShares; }
 

@@ -65,7 +65,9 @@ namespace cda {
 
 namespace {
 
-constexpr uint32_t kProofWaves = 4;        // segments, or share units, per workgroup
+static_assert(kSegMaxSquares == CDA_SET_MAX_SQUARES, "a segment's row word names every square a set can hold");
+
+constexpr uint32_t kProofWaves = 4;       // segments, or share units, per workgroup
 constexpr uint32_t kProofSlots = 2 * kProofMaxD + 2;   // proof nodes, the row root, the namespace or absence leaf
 // The single-range call returns outputs of up to this many bytes in one copy (regions_out): measured against one
 // copy per output, it is faster up to 1 MiB of shares and slower from 2 MiB (profiles/resident_proof_refactor.txt).
@@ -92,18 +94,33 @@ __device__ __forceinline__ SegEntry load_seg(const SegEntry* p) {
     return SegEntry{lo.x, lo.y, lo.z, lo.w, (uint64_t)hi.x | ((uint64_t)hi.y << 32), hi.z, hi.w};
 }
 
+// The square a segment is served from: a.sq itself, or (kSet) the member of the set that the segment's row
+// word names, a.sq then holding the arenas' bases (square_set.hip) -- with the segment's row.
+template <bool kSet>
+__device__ __forceinline__ ResidentView seg_view(const ShareProofsArgs& a, const SetStrides& sq, const SegEntry& e,
+                                                 uint32_t* row) {
+    if constexpr (kSet) {
+        *row = seg_row(e.row);
+        return member_view(a.sq, sq, seg_square(e.row));
+    } else {
+        *row = e.row;
+        return a.sq;
+    }
+}
+
 // One wavefront per segment; every wave of the workgroup reaches every barrier.
-template <bool SUB>
-__device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*stage)[stage_row(kProofSlots)],
-                                           uint32_t* tiles) {
+template <bool SUB, bool kSet>
+__device__ __forceinline__ void proof_part(const ShareProofsArgs& a, const SetStrides& sq,
+                                           uint4 (*stage)[stage_row(kProofSlots)], uint32_t* tiles) {
     const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const uint32_t g = blockIdx.x * kProofWaves + wave;
     const bool live = g < a.n_segs;   // uniform over the wave
-    const ResidentView& v = a.sq;
-    const uint32_t W = 2 * v.k, D = v.log_w, A = D + 1;
+    const uint32_t W = 2 * a.sq.k, D = a.sq.log_w, A = D + 1;   // one width for every member of a set
     SegEntry e{};
     if (live) e = load_seg(a.segs + g);
-    const uint32_t row = e.row, s0 = e.range & 0xFFFFu, e0 = live ? (e.range >> 16) & kSegEndMask : 1u;
+    uint32_t row;
+    const ResidentView v = seg_view<kSet>(a, sq, e, &row);
+    const uint32_t s0 = e.range & 0xFFFFu, e0 = live ? (e.range >> 16) & kSegEndMask : 1u;
     const uint32_t cnt = live ? range_proof_count(D, s0, e0) : 0u;
     const bool first = live && e.first_cell == row * W + s0;   // the proof's first segment
     const bool absent = (e.range & kSegAbsence) != 0;          // an absence segment: its leaf follows the row root
@@ -171,7 +188,8 @@ __device__ __forceinline__ void proof_part(const ShareProofsArgs& a, uint4 (*sta
 }
 
 // One wavefront per unit of at most kUnitShares shares of one segment.
-__device__ __forceinline__ void share_part(const ShareProofsArgs& a) {
+template <bool kSet>
+__device__ __forceinline__ void share_part(const ShareProofsArgs& a, const SetStrides& sq) {
     const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const uint32_t u = (blockIdx.x - a.proof_blocks) * kProofWaves + wave;
     if (u >= a.n_units) return;   // uniform over the wave; this part has no barrier
@@ -183,48 +201,52 @@ __device__ __forceinline__ void share_part(const ShareProofsArgs& a) {
         else hi = mid - 1;
     }
     const SegEntry e = load_seg(a.segs + lo);
-    const uint32_t W = 2 * a.sq.k, s0 = e.range & 0xFFFFu, e0 = (e.range >> 16) & kSegEndMask;
+    uint32_t row;
+    const ResidentView v = seg_view<kSet>(a, sq, e, &row);
+    const uint32_t W = 2 * v.k, s0 = e.range & 0xFFFFu, e0 = (e.range >> 16) & kSegEndMask;
     const uint32_t at = (u - e.unit_off) * kUnitShares;   // first share of the unit within the segment
     const uint32_t cnt = min(kUnitShares, e0 - s0 - at);
-    const uint4* src = reinterpret_cast<const uint4*>(a.sq.eds + ((uint64_t)e.row * W + s0 + at) * kShare);
+    const uint4* src = reinterpret_cast<const uint4*>(v.eds + ((uint64_t)row * W + s0 + at) * kShare);
     uint4* dst = a.shares ? reinterpret_cast<uint4*>(a.shares + (e.share_off + at) * kShare) : nullptr;
     constexpr uint32_t V = kShare / 16;   // 16-byte pieces per share
     const uint32_t part = lane % V;
     // the proof's first namespace: bytes 0..28 are pieces 0 and 1 without the last three bytes
     const bool ns_lane = a.flags && part < 2;
     uint4 ref = make_uint4(0, 0, 0, 0);
-    if (ns_lane) ref = reinterpret_cast<const uint4*>(a.sq.eds + (uint64_t)e.first_cell * kShare)[part];
+    if (ns_lane) ref = reinterpret_cast<const uint4*>(v.eds + (uint64_t)e.first_cell * kShare)[part];
     const uint32_t last_mask = part == 1 ? 0x000000FFu : 0xFFFFFFFFu;
     bool differs = false;
     constexpr uint32_t kIters = kUnitShares * V / 64;   // pieces per lane: all loads in flight, then the stores
     const bool wanted = dst || ns_lane;
-    uint4 v[kIters];
+    uint4 x[kIters];
 #pragma unroll
     for (uint32_t it = 0; it < kIters; it++) {
         const uint32_t q = it * 64 + lane;   // piece q of the unit: share q / V
-        v[it] = make_uint4(0, 0, 0, 0);
-        if (q < cnt * V && wanted) v[it] = src[q];
+        x[it] = make_uint4(0, 0, 0, 0);
+        if (q < cnt * V && wanted) x[it] = src[q];
     }
 #pragma unroll
     for (uint32_t it = 0; it < kIters; it++) {
         const uint32_t q = it * 64 + lane;
         if (q < cnt * V && wanted) {
-            if (dst) dst[q] = v[it];
+            if (dst) dst[q] = x[it];
             if (ns_lane)
-                differs |= v[it].x != ref.x || v[it].y != ref.y || v[it].z != ref.z ||
-                           ((v[it].w ^ ref.w) & last_mask) != 0;
+                differs |= x[it].x != ref.x || x[it].y != ref.y || x[it].z != ref.z ||
+                           ((x[it].w ^ ref.w) & last_mask) != 0;
         }
     }
     if (a.flags && __ballot(differs) != 0 && lane == 0)
         atomicAnd(a.flags + e.proof / 4, ~(0xFFu << (8 * (e.proof % 4))));
 }
 
-template <bool SUB>
-__global__ __launch_bounds__(64 * kProofWaves) void share_proofs_kernel(const ShareProofsArgs a) {
+// kSet: the table's segments name their squares (segment_table.h seg_row_word), a.sq holds the bases of a
+// set's arenas and sq their per-square strides; else every segment is of the square a.sq and sq is unused.
+template <bool SUB, bool kSet>
+__global__ __launch_bounds__(64 * kProofWaves) void share_proofs_kernel(const ShareProofsArgs a, const SetStrides sq) {
     __shared__ uint4 stage[kProofWaves][stage_row(kProofSlots)];
     __shared__ uint32_t tiles[kProofWaves];
-    if (blockIdx.x < a.proof_blocks) proof_part<SUB>(a, stage, tiles);   // uniform over the workgroup
-    else share_part(a);
+    if (blockIdx.x < a.proof_blocks) proof_part<SUB, kSet>(a, sq, stage, tiles);   // uniform over the workgroup
+    else share_part<kSet>(a, sq);
 }
 
 }  // namespace
@@ -242,7 +264,27 @@ int Engine::square_share_proof(ResidentSquare* sq, uint32_t start, uint32_t end,
 // M = 2 log2 W, and nmt_count[g] of them are valid.  one_copy_max: outputs up to this size return in one copy.
 int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, const uint32_t* ends, uint32_t n,
                                 const cda_share_proofs_out& o, uint32_t* nmt_count, size_t one_copy_max) {
-    const uint32_t k = sq->k, W = 2 * k, D = sq->log_w, A = D + 1, M = 2 * D;
+    return range_share_proofs(sq, nullptr, nullptr, starts, ends, n, o, nmt_count, one_copy_max);
+}
+
+// cda_square_set_share_proofs: range i of member squares[i].  The sizes of a range do not depend on the
+// square, so plan, table and outputs are the single square's; every segment names its square beside its row.
+int Engine::square_set_share_proofs(ResidentSquareSet* set, const uint32_t* squares, const uint32_t* starts,
+                                    const uint32_t* ends, uint32_t n, const cda_share_proofs_out& o) {
+    if (n && !squares) return fail(CDA_ERR_INVALID, "null squares");
+    if (n && (!starts || !ends)) return fail(CDA_ERR_INVALID, "null buffer");   // the single square's text
+    for (uint32_t i = 0; i < n; i++)
+        if (squares[i] >= set->n)
+            return fail(CDA_ERR_INVALID, "range " + std::to_string(i) + ": square " + std::to_string(squares[i]) +
+                                             " is not below the set's " + std::to_string(set->n) + " squares");
+    return range_share_proofs(nullptr, set, squares, starts, ends, n, o, nullptr, 0);
+}
+
+// The ranges of one square (sq), or of the members squares[i] of a set.
+int Engine::range_share_proofs(ResidentSquare* sq, ResidentSquareSet* set, const uint32_t* squares,
+                               const uint32_t* starts, const uint32_t* ends, uint32_t n,
+                               const cda_share_proofs_out& o, uint32_t* nmt_count, size_t one_copy_max) {
+    const uint32_t k = sq ? sq->k : set->k, W = 2 * k, D = sq ? sq->log_w : set->log_w, A = D + 1, M = 2 * D;
     ShareProofsPlan plan;
     const std::string bad = share_proofs_plan(k, starts, ends, n, &plan);
     if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
@@ -263,11 +305,11 @@ int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, cons
     uint32_t g = 0, node_at = 0, unit_at = 0;
     uint64_t share_at = 0;
     for (uint32_t i = 0; i < n; i++) {
-        const uint32_t first_cell = (starts[i] / k) * W + starts[i] % k;
+        const uint32_t first_cell = (starts[i] / k) * W + starts[i] % k, square = squares ? squares[i] : 0u;
         for_each_segment(k, i, starts[i], ends[i], [&](const ShareProofSegment& sg) {
             const uint32_t count = range_proof_count(D, sg.s0, sg.e0);
-            segs[g] = SegEntry{sg.row, sg.s0 | (sg.e0 << 16), nmt_count ? g * M : node_at, unit_at, share_at, i,
-                               first_cell};
+            segs[g] = SegEntry{seg_row_word(sg.row, square), sg.s0 | (sg.e0 << 16), nmt_count ? g * M : node_at,
+                               unit_at, share_at, i, first_cell};
             if (nmt_count) nmt_count[g] = count;
             if (o.nmt_start) o.nmt_start[g] = (int32_t)sg.s0;
             if (o.nmt_end) o.nmt_end[g] = (int32_t)sg.e0;
@@ -298,7 +340,7 @@ int Engine::square_share_proofs(ResidentSquare* sq, const uint32_t* starts, cons
     em.namespaces = o.namespaces;
     em.one_namespace = o.one_namespace;
     em.one_copy_max = one_copy_max;
-    return emit_segments(sq, em);
+    return emit_segments(sq, set, em);
 }
 
 // cda_square_commitment_proofs: a blob is the share range [start, start + share_len) after NextShareIndex, and
@@ -366,13 +408,26 @@ int Engine::square_commitment_proofs(ResidentSquare* sq, const uint32_t* starts,
     em.subtree_roots = o.subtree_roots;
     em.commitments = o.commitments;
     em.stage = kStageCommitmentProofs;
-    return emit_segments(sq, em);
+    return emit_segments(sq, nullptr, em);
 }
 
 // The table-to-launch half of both producers (share ranges above, namespaces in namespace_proofs.hip): one
-// upload, one launch whatever the table holds, the requested outputs back.
-int Engine::emit_segments(ResidentSquare* sq, const SegmentEmit& em) {
+// upload, one launch whatever the table holds, the requested outputs back.  A square, or a set (sq == NULL):
+// the table's segments then name their squares, the kernel is the set instantiation over the arenas' bases
+// and the scratch is the set's own.
+int Engine::emit_segments(ResidentSquare* sq, ResidentSquareSet* set, const SegmentEmit& em) {
     const uint32_t S = em.n_segs;
+    DevBuf& scratch = sq ? sq->scratch : set->scratch;
+    // SUB has no set instantiation: refuse such a table before anything is enqueued
+    if (!sq && (em.subtree_roots || em.commitments))
+        return fail(CDA_ERR_INVALID, "subtree segments are not served across a set");
+    const ResidentView view = sq ? sq->view()
+                                 : ResidentView{set->eds.as<uint8_t>(), set->levels.as<uint8_t>(),
+                                                set->col_levels.as<uint8_t>(), set->roots_slots.as<uint8_t>(),
+                                                set->rfc.as<uint32_t>(), set->k, set->log_w};
+    const SetStrides st = sq ? SetStrides{}
+                             : SetStrides{set->eds_sq, set->levels_sq, set->col_levels_sq, set->roots_slots_sq,
+                                          set->rfc_sq};
     // scratch: the upload, then one region per requested output; the flags lie inside the upload
     OutRegions out(em.up.size() * 4);
     const auto r_nd = out.add(em.nodes, em.node_slots * kNode), r_rt = out.add(em.row_roots, (size_t)S * kNode),
@@ -386,10 +441,10 @@ int Engine::emit_segments(ResidentSquare* sq, const SegmentEmit& em) {
     // scratch behind the outputs: the subtree roots' leaf digests
     const size_t dig_off = out.total(), dig_bytes = em.commitments ? em.n_roots * 32 : 0;
     hipStream_t s = stream_;
-    CDA_TRY(ensure(sq->scratch, out.total() + dig_bytes, "hipMalloc"));
-    uint8_t* scr = sq->scratch.as<uint8_t>();
+    CDA_TRY(ensure(scratch, out.total() + dig_bytes, "hipMalloc"));
+    uint8_t* scr = scratch.as<uint8_t>();
     CDA_TRY(h2d(scr, em.up.data(), em.up.size() * 4, s, "H2D share proofs"));
-    ShareProofsArgs a{sq->view(), reinterpret_cast<const SegEntry*>(scr), S, 0, 0, r_nd.dev(scr), r_rt.dev(scr),
+    ShareProofsArgs a{view, reinterpret_cast<const SegEntry*>(scr), S, 0, 0, r_nd.dev(scr), r_rt.dev(scr),
                       r_lh.dev(scr), r_au.dev(scr), r_sh.dev(scr), r_ns.dev(scr),
                       reinterpret_cast<uint32_t*>(r_fl.dev(scr)), r_al.dev(scr), r_sr.dev(scr),
                       em.commitments ? reinterpret_cast<uint32_t*>(scr + dig_off) : nullptr};
@@ -400,8 +455,10 @@ int Engine::emit_segments(ResidentSquare* sq, const SegmentEmit& em) {
     const uint32_t blocks = a.proof_blocks + (a.n_units + kProofWaves - 1) / kProofWaves;
     if (blocks) {
         if (em.stage >= 0) mark_begin(em.stage, s);
-        if (sub) hipLaunchKernelGGL(share_proofs_kernel<true>, dim3(blocks), dim3(64 * kProofWaves), 0, s, a);
-        else hipLaunchKernelGGL(share_proofs_kernel<false>, dim3(blocks), dim3(64 * kProofWaves), 0, s, a);
+        const dim3 grid(blocks), wg(64 * kProofWaves);
+        if (!sq) hipLaunchKernelGGL((share_proofs_kernel<false, true>), grid, wg, 0, s, a, st);
+        else if (sub) hipLaunchKernelGGL((share_proofs_kernel<true, false>), grid, wg, 0, s, a, st);
+        else hipLaunchKernelGGL((share_proofs_kernel<false, false>), grid, wg, 0, s, a, st);
         if (em.stage >= 0) mark_end(s);
         CDA_TRY(launched("share proofs"));
     }

@@ -88,9 +88,11 @@ struct VerifyBatch {
     const uint64_t* share_off;   // first share of every segment in `shares`
     const uint8_t* absence_leaf; // per segment, node_len bytes: the leaf an absence segment folds
     const uint32_t* seg_row;     // per segment: its row in the DAH
-    const uint8_t* dah_roots;    // n_rows row roots of the DAH
+    const uint8_t* dah_roots;    // n_rows row roots of the DAH (of every uploaded DAH, one behind the other)
     uint32_t n_rows, n_nodes;
     uint8_t* comp_ok;            // per segment, preset to 1: no proof node contradicts completeness
+    // last, so that every other field keeps its place among the kernels' arguments
+    const uint32_t* query_dah;   // several DAHs (vn_verdict_kernel<true>): per query, which of them
 };
 
 // Leaf nodes of every share of the batch.  FAST: ns_len 29, share_len 512,
@@ -341,16 +343,20 @@ __global__ __launch_bounds__(256) void vn_complete_kernel(const VerifyBatch b) {
 }
 
 // One lane per query: the rows the DAH selects against the answer's rows (1), then the segments' folds and
-// absence leaves (2), then completeness (3).
+// absence leaves (2), then completeness (3).  kSet: the queries are checked against several DAHs, query p
+// against the n_rows roots of DAH query_dah[p].
+template <bool kSet>
 __global__ __launch_bounds__(256) void vn_verdict_kernel(const VerifyBatch b) {
     const uint32_t p = blockIdx.x * 256 + threadIdx.x;
     if (p >= b.n_proofs) return;
     const uint8_t* ns = b.namespaces + (size_t)p * b.ns_len;
     const uint32_t s0 = b.seg_off[p], s1 = b.seg_off[p + 1];
+    const uint8_t* dah = b.dah_roots;
+    if constexpr (kSet) dah += (size_t)b.query_dah[p] * b.n_rows * b.node_len;
     uint32_t s = s0;
     bool rows_ok = true;
     for (uint32_t r = 0; r < b.n_rows; r++) {
-        const uint8_t* root = b.dah_roots + (size_t)r * b.node_len;
+        const uint8_t* root = dah + (size_t)r * b.node_len;
         if (vn_cmp(root, ns, b.ns_len) > 0 || vn_cmp(ns, root + b.ns_len, b.ns_len) > 0) continue;
         if (s < s1 && b.seg_row[s] == r) s++;
         else rows_ok = false;
@@ -526,6 +532,15 @@ int Engine::share_proofs_verify(const cda_share_proof_batch* b, uint8_t* verdict
 // absence segment folds the one leaf it brings.  Five launches and one fill per batch.
 int Engine::namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const cda_namespace_proof_batch* b,
                                     uint8_t* verdict) {
+    return namespace_proofs_verify_set(k, row_roots, 1, nullptr, b, verdict);
+}
+
+// Against several DAHs (cda_namespace_proofs_verify_set): only the DAHs that a query names go up, each once,
+// in the order of their first query, and query_dah counts in those.  squares == NULL is the one-DAH call: no
+// such array, the kernels and the uploads it always had.
+int Engine::namespace_proofs_verify_set(uint32_t k, const uint8_t* row_roots, uint32_t n_squares,
+                                        const uint32_t* squares, const cda_namespace_proof_batch* b,
+                                        uint8_t* verdict) {
     if (!b) return fail(CDA_ERR_INVALID, "null batch");
     CDA_TRY(check_width(k));
     const uint32_t P = b->n_queries, W = 2 * k;
@@ -533,6 +548,28 @@ int Engine::namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const 
     if (!verdict) return fail(CDA_ERR_INVALID, "null verdict buffer");
     if (!row_roots || !b->namespaces || !b->seg_off) return fail(CDA_ERR_INVALID, "null row_roots / namespaces / seg_off");
     auto query = [](uint32_t q, const std::string& what) { return "query " + std::to_string(q) + ": " + what; };
+    const bool set = squares != nullptr;
+    if (!set && n_squares != 1) return fail(CDA_ERR_INVALID, "null squares");
+    std::vector<uint32_t> query_dah, named;   // per query; the squares whose DAHs go up
+    if (set) {
+        for (uint32_t q = 0; q < P; q++)
+            if (squares[q] >= n_squares)
+                return fail(CDA_ERR_INVALID, query(q, "square " + std::to_string(squares[q]) + " is not below the " +
+                                                          std::to_string(n_squares) + " squares of row_roots"));
+        std::vector<uint32_t> slot(n_squares, UINT32_MAX);
+        query_dah.resize(P);
+        for (uint32_t q = 0; q < P; q++) {
+            if (slot[squares[q]] == UINT32_MAX) {
+                slot[squares[q]] = (uint32_t)named.size();
+                named.push_back(squares[q]);
+            }
+            query_dah[q] = slot[squares[q]];
+        }
+    }
+    // the trusted row root of segment s of query q
+    auto dah_root = [&](uint32_t q, uint32_t row) {
+        return row_roots + ((size_t)(set ? squares[q] : 0u) * W + row) * kNode;
+    };
     for (uint32_t q = 0; q < P; q++) {
         bool parity = true;
         for (int j = 0; j < kNs; j++) parity = parity && b->namespaces[(size_t)q * kNs + j] == 0xFFu;
@@ -578,7 +615,7 @@ int Engine::namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const 
                        " shares of the inclusion segments before it");
         share_at += kind == CDA_NAMESPACE_INCLUSION ? (uint64_t)(en - st) : 0;
         leaf_off[s + 1] = leaf_off[s] + (uint64_t)(en - st);
-        memcpy(seg_roots.data() + (size_t)s * kNode, row_roots + (size_t)b->row[s] * kNode, kNode);
+        memcpy(seg_roots.data() + (size_t)s * kNode, dah_root(seg_query[s], b->row[s]), kNode);
     }
     if (S && b->node_off[S] != b->n_nodes)
         return fail(CDA_ERR_INVALID, "node_off ends at " + std::to_string(b->node_off[S]) + ", n_nodes is " +
@@ -606,15 +643,22 @@ int Engine::namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const 
         total += (pc.bytes + 15) & ~(size_t)15;
         return pc;
     };
+    // the named DAHs, gathered so that they go up in one copy
+    const size_t dah_bytes = (size_t)W * kNode;
+    std::vector<uint8_t> dahs(named.size() * dah_bytes);
+    for (size_t i = 0; i < named.size(); i++)
+        memcpy(dahs.data() + i * dah_bytes, row_roots + named[i] * dah_bytes, dah_bytes);
     const Piece p_ns = piece(b->namespaces, (size_t)P * kNs), p_seg = piece(b->seg_off, (size_t)(P + 1) * 4),
                 p_sq = piece(seg_query.data(), (size_t)S * 4), p_row = piece(b->row, (size_t)S * 4),
                 p_kind = piece(b->kind, S), p_st = piece(b->nmt_start, (size_t)S * 4),
                 p_en = piece(b->nmt_end, (size_t)S * 4), p_no = piece(b->node_off, S ? (size_t)(S + 1) * 4 : 0),
                 p_nodes = piece(b->nodes, (size_t)n_nodes * kNode), p_rr = piece(seg_roots.data(), (size_t)S * kNode),
-                p_dah = piece(row_roots, (size_t)W * kNode), p_lo = piece(leaf_off.data(), (size_t)(S + 1) * 8),
+                p_dah = piece(set ? dahs.data() : row_roots, (set ? named.size() : 1) * dah_bytes),
+                p_lo = piece(leaf_off.data(), (size_t)(S + 1) * 8),
                 p_so = piece(b->share_off, S ? (size_t)(S + 1) * 8 : 0),
                 p_sh = piece(b->shares, (size_t)share_at * kShare),
-                p_al = piece(b->absence_leaf, (size_t)S * kNode);
+                p_al = piece(b->absence_leaf, (size_t)S * kNode),
+                p_qd = piece(set ? query_dah.data() : nullptr, (size_t)P * 4);
     CDA_TRY(ensure(vp_in_, total + 16, "hipMalloc proof batch"));
     const size_t scr_nodes = ((size_t)n_leaves * kSlot + 15) & ~(size_t)15;
     const size_t flags = ((size_t)S + 15) & ~(size_t)15;
@@ -622,7 +666,7 @@ int Engine::namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const 
     CDA_TRY(ensure(vp_scratch_, 2 * scr_nodes + node_slots + 2 * flags + P + 16, "hipMalloc proof scratch"));
     uint8_t* in = vp_in_.as<uint8_t>();
     for (const Piece* pc : {&p_ns, &p_seg, &p_sq, &p_row, &p_kind, &p_st, &p_en, &p_no, &p_nodes, &p_rr, &p_dah, &p_lo,
-                            &p_so, &p_sh, &p_al})
+                            &p_so, &p_sh, &p_al, &p_qd})
         if (pc->bytes) CDA_TRY(h2d(in + pc->off, pc->host, pc->bytes, s, "H2D namespace proof batch"));
     uint8_t* scr = vp_scratch_.as<uint8_t>();
     VerifyBatch v{};
@@ -654,6 +698,7 @@ int Engine::namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const 
     v.absence_leaf = in + p_al.off;
     v.seg_row = reinterpret_cast<const uint32_t*>(in + p_row.off);
     v.dah_roots = in + p_dah.off;
+    v.query_dah = reinterpret_cast<const uint32_t*>(in + p_qd.off);
     v.n_rows = W;
     v.n_nodes = n_nodes;
     if (S) {
@@ -667,7 +712,8 @@ int Engine::namespace_proofs_verify(uint32_t k, const uint8_t* row_roots, const 
             CDA_TRY(launched("namespace proof completeness"));
         }
     }
-    hipLaunchKernelGGL(vn_verdict_kernel, dim3((P + 255) / 256), dim3(256), 0, s, v);
+    if (set) hipLaunchKernelGGL(vn_verdict_kernel<true>, dim3((P + 255) / 256), dim3(256), 0, s, v);
+    else hipLaunchKernelGGL(vn_verdict_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, s, v);
     CDA_TRY(launched("namespace proof verdicts"));
     std::vector<uint8_t> out(P);
     CDA_TRY(d2h(out.data(), v.verdict, P, s, "D2H verdicts"));

@@ -53,6 +53,10 @@
  *                          ProveNamespace's proofs (EXT nmt v0.22.0; absence proofs
  *                          included), the rows chosen as GetSharesByNamespace chooses
  *                          them from the DAH, and Proof.VerifyNamespace of the answers
+ *   cda_square_set_namespace_plan / cda_square_set_namespace_proofs /
+ *   cda_square_set_share_proofs / cda_namespace_proofs_verify_set
+ *                          the same queries across a set of resident squares (a range
+ *                          of heights) in the launches of one square's call
  *   cda_shares_parse_plan / cda_shares_parse / cda_square_parse_plan / cda_square_parse
  *                          go-square shares.ParseShares / ParseTxs / ParseBlobs (EXT v1.1.0): a
  *                          square's shares back into its transactions, IndexWrappers and blobs,
@@ -718,6 +722,40 @@ typedef struct cda_namespace_proof_batch {
 } cda_namespace_proof_batch;
 int cda_namespace_proofs_verify(cda_ctx *ctx, uint32_t k, const uint8_t *row_roots,
                                 const cda_namespace_proof_batch *b, uint8_t *verdict);
+
+/* ---- Namespace and share-range proofs across a set of resident squares ---------
+ * What a node serves from a range of heights, in the launches of ONE square's call whatever n and however
+ * many members are named: query i is the namespace namespaces + 29 i of member squares[i], range i is
+ * [starts[i], ends[i]) of the ODS of member squares[i].  All members share k, so the output structs, their
+ * layouts and their NULL-output rules are those of cda_square_namespace_plan / _proofs and
+ * cda_square_share_proofs, unchanged: query i's segments are the bytes that cda_square_namespace_proofs on
+ * member squares[i] answers for that namespace alone, placed in request order, and so for the ranges.  The
+ * sizes of share ranges do not depend on the square: cda_square_share_proofs_plan sizes the set call as it is.
+ *   cda_square_set_namespace_plan    one search launch, one copy back of n*k*4 bytes;
+ *   cda_square_set_namespace_proofs  one search launch, one host pass, one proof launch;
+ *   cda_square_set_share_proofs      one proof launch;
+ * each with one upload of its requests.  All host pointers; complete on return.
+ * cda_namespace_proofs_verify_set is cda_namespace_proofs_verify against the DAHs of n_squares squares
+ * (row_roots: n_squares*2k*90, square by square, as cda_square_set_dah returns them): query q is checked
+ * against the DAH squares[q].  A prover's arrays plus its squares array make the batch by pointer assignment;
+ * verdicts, launches (five and one fill) and structural checks are those of cda_namespace_proofs_verify, which
+ * equals this call with n_squares = 1 and squares all zero.  Only the DAHs that a query names are uploaded.
+ * Share proofs of a set go to cda_share_proofs_verify as they are, with each proof's own data root.
+ * Validated on the host before anything is enqueued, outputs untouched: CDA_ERR_INVALID with a message naming
+ * the query or range and the field for a null array, for squares[i] not below the set's count or n_squares
+ * ("query 3: square 9 is not below the set's 4 squares"), for a query equal to ParitySharesNamespace, and for
+ * everything the single-square calls check, with their texts.  n == 0 returns CDA_OK.  A namespace query that
+ * names a member whose push order failed answers CDA_ERR_PUSH_ORDER, naming the query, the square and the
+ * violation (cda_push_order_detail is set), nothing written; share proofs of such a member are served like
+ * any other. */
+int cda_square_set_namespace_plan(cda_square_set *set, const uint32_t *squares, const uint8_t *namespaces,
+                                  uint32_t n, cda_namespace_plan_t *out);
+int cda_square_set_namespace_proofs(cda_square_set *set, const uint32_t *squares, const uint8_t *namespaces,
+                                    uint32_t n, const cda_namespace_proofs_out *out);
+int cda_namespace_proofs_verify_set(cda_ctx *ctx, uint32_t k, const uint8_t *row_roots, uint32_t n_squares,
+                                    const uint32_t *squares, const cda_namespace_proof_batch *b, uint8_t *verdict);
+int cda_square_set_share_proofs(cda_square_set *set, const uint32_t *squares, const uint32_t *starts,
+                                const uint32_t *ends, uint32_t n, const cda_share_proofs_out *out);
 
 /* ---- Blob inclusion by share commitment ------------------------------------------
  * The proof the square layout was designed for (specs/src/specs/data_square_layout.md): that the blob a
