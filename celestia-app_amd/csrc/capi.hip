@@ -137,6 +137,10 @@ int not_pow2(cda::Engine& e, uint32_t n) {
     return e.fail(CDA_ERR_NOT_POW2, buf);
 }
 
+// The widest square the library extends (Engine::check_width).  The host
+// entry points say so before they stage a byte of a wider one.
+int too_wide(cda::Engine& e) { return e.fail(CDA_ERR_INVALID, "square width must be a power of two <= 1024"); }
+
 int plan_square(const uint8_t* txs, const uint64_t* tx_off, uint32_t n_txs, uint32_t max_square_size,
                 uint32_t threshold, int mode, cda::square::Plan* p, std::string* err) {
     if (mode != CDA_SQUARE_CONSTRUCT && mode != CDA_SQUARE_BUILD) {
@@ -213,6 +217,7 @@ int cda_extend_shares(cda_ctx* ctx, const uint8_t* ods, uint32_t n_shares, uint8
     return guarded(ctx, [&](cda::Engine& e) -> int {
         uint32_t k;
         if (!square_width(n_shares, &k)) return not_pow2(e, n_shares);
+        if (k > 1024) return too_wide(e);
         if (!ods || !eds) return e.fail(CDA_ERR_INVALID, "null buffer");
         return e.host_extend(ods, k, eds);
     });
@@ -222,6 +227,7 @@ int cda_dah_from_eds(cda_ctx* ctx, const uint8_t* eds, uint32_t w, uint8_t* row_
                      uint8_t* data_root) {
     return guarded(ctx, [&](cda::Engine& e) -> int {
         if (w < 2 || (w & (w - 1))) return e.fail(CDA_ERR_INVALID, "EDS width must be a power of two >= 2");
+        if (w > 2048) return too_wide(e);
         if (!eds || !row_roots || !col_roots || !data_root) return e.fail(CDA_ERR_INVALID, "null buffer");
         return e.host_dah(eds, w / 2, row_roots, col_roots, data_root);
     });
@@ -232,6 +238,7 @@ int cda_extend_dah(cda_ctx* ctx, const uint8_t* ods, uint32_t n_shares, uint8_t*
     return guarded(ctx, [&](cda::Engine& e) -> int {
         uint32_t k;
         if (!square_width(n_shares, &k)) return not_pow2(e, n_shares);
+        if (k > 1024) return too_wide(e);
         if (!ods || !row_roots || !col_roots || !data_root) return e.fail(CDA_ERR_INVALID, "null buffer");
         return e.host_extend_dah(ods, k, 1, eds, row_roots, col_roots, data_root, nullptr);
     });
@@ -241,6 +248,7 @@ int cda_extend_dah_batch(cda_ctx* ctx, const uint8_t* ods, uint32_t k, uint32_t 
                          uint8_t* col_roots, uint8_t* data_roots, int32_t* status) {
     return guarded(ctx, [&](cda::Engine& e) -> int {
         if (k == 0 || (k & (k - 1))) return not_pow2(e, k * k);
+        if (k > 1024) return too_wide(e);
         if (n == 0) return CDA_OK;
         if (!ods || !row_roots || !col_roots || !data_roots) return e.fail(CDA_ERR_INVALID, "null buffer");
         return e.host_extend_dah(ods, k, n, eds, row_roots, col_roots, data_roots, status);
@@ -251,6 +259,7 @@ int cda_extend_dah_batch_ex(cda_ctx* ctx, const uint8_t* ods, uint32_t k, uint32
                             uint8_t* row_roots, uint8_t* col_roots, uint8_t* data_roots, int32_t* status) {
     return guarded(ctx, [&](cda::Engine& e) -> int {
         if (k == 0 || (k & (k - 1))) return not_pow2(e, k * k);
+        if (k > 1024) return too_wide(e);
         if (eds_mode != CDA_EDS_FULL && eds_mode != CDA_EDS_SKIP_Q0 && eds_mode != CDA_EDS_PARITY)
             return e.fail(CDA_ERR_INVALID, "unknown eds_mode");
         if (n == 0) return CDA_OK;
@@ -278,7 +287,8 @@ int cda_extend_dah_device(cda_ctx* ctx, const void* d_ods, uint32_t k, uint32_t 
 
 int cda_reserve(cda_ctx* ctx, uint32_t k, uint32_t n) {
     return guarded(ctx, [&](cda::Engine& e) -> int {
-        if (k == 0 || (k & (k - 1)) || k > 1024) return not_pow2(e, k * k);
+        if (k == 0 || (k & (k - 1))) return not_pow2(e, k * k);
+        if (k > 1024) return too_wide(e);
         return e.reserve(k, n);
     });
 }
@@ -316,6 +326,7 @@ int cda_data_root(cda_ctx* ctx, const uint8_t* row_roots, const uint8_t* col_roo
             return CDA_OK;
         }
         if (w & (w - 1)) return e.fail(CDA_ERR_UNSUPPORTED, "root count must be a power of two");
+        if (w > 2048) return e.fail(CDA_ERR_UNSUPPORTED, "more than 2048 roots per axis");
         if (!row_roots || !col_roots) return e.fail(CDA_ERR_INVALID, "null buffer");
         return e.host_data_root(row_roots, col_roots, w, data_root);
     });

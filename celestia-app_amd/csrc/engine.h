@@ -504,6 +504,8 @@ class Engine {
     int top_fuse_ = -1;   // CDA_TOP_FUSE (tuning / A-B): -1 auto, 0 off, N = nodes per tree
     int top_wide_ = 2;    // CDA_TOP_WIDE: levels the tree top absorbs below the lane-pair level
     int check_width(uint32_t k);   // CDA_ERR_INVALID unless k is a power of two <= 1024
+    // RFC-6962 root of one square's n_items root slots (rows then columns), wherever no tree top left digests
+    int enqueue_data_root(const uint8_t* d_root_slots, uint32_t n_items, uint8_t* d_root, hipStream_t s);
     // The reference's ErrInvalidPushOrder text from the two namespaces (NULL: a
     // parity cell's, all 0xFF), and the one for the first violating square of
     // a batch's push-order words (push_order.h), which also sets po_*.

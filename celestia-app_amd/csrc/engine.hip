@@ -703,7 +703,16 @@ int Engine::enqueue_split_combine(const uint8_t* d_row_sub, uint32_t parts, uint
     CDA_TRY(check(hipMemcpyAsync(rs + (size_t)W * kSlot, d_col_slots, (size_t)W * kSlot, hipMemcpyDeviceToDevice, s),
             "copy"));
     CDA_TRY(check(launch_slots_to_roots(rs, 2 * W, d_rows, d_cols, W, s), "pack roots"));
-    return check(launch_data_root(rs, 2 * W, 1, d_root, s), "data root");
+    return enqueue_data_root(rs, 2 * W, d_root, s);
+}
+
+// data_root_kernel keeps 1.5 digests per item in LDS: 192 KiB for the 4096
+// roots of a k = 1024 square, more than a CU has (launch_data_root refuses it).
+// That width takes the two-launch form, the leaf digests in dig_.
+int Engine::enqueue_data_root(const uint8_t* d_root_slots, uint32_t n_items, uint8_t* d_root, hipStream_t s) {
+    if (n_items <= 2048) return check(launch_data_root(d_root_slots, n_items, 1, d_root, s), "data root");
+    CDA_TRY(ensure(dig_, (size_t)n_items * 32, "hipMalloc digests"));
+    return check(launch_data_root_slots(d_root_slots, n_items, 1, dig_.as<uint32_t>(), d_root, s), "data root");
 }
 
 int Engine::enqueue_extend_dah_serial(const uint8_t* d_ods, uint32_t k, uint32_t n, uint8_t* d_eds,
@@ -1202,7 +1211,7 @@ int Engine::host_data_root(const uint8_t* rows, const uint8_t* cols, uint32_t w,
     CDA_TRY(ensure(h_roots_, 32, "hipMalloc"));
     hipStream_t s = stream_;
     CDA_TRY(h2d(root_slots_.ptr, slots.data(), slots.size(), s, "H2D"));
-    CDA_TRY(check(launch_data_root(root_slots_.as<uint8_t>(), 2 * w, 1, h_roots_.as<uint8_t>(), s), "data root"));
+    CDA_TRY(enqueue_data_root(root_slots_.as<uint8_t>(), 2 * w, h_roots_.as<uint8_t>(), s));
     CDA_TRY(d2h(root, h_roots_.ptr, 32, s, "D2H"));
     return sync(s);
 }

@@ -142,6 +142,26 @@ enum {
 
 typedef struct cda_ctx cda_ctx;
 
+/* ---- Square widths --------------------------------------------------------------
+ * The calls that extend, hash, prove and sample take squares of ODS width
+ * k = 1 .. 1024 (a power of two; EDS width 2k <= 2048).  A wider square is
+ * answered with CDA_ERR_INVALID, "square width must be a power of two <=
+ * 1024", before a buffer is read or staged: cda_extend_shares,
+ * cda_dah_from_eds, cda_extend_dah, cda_extend_dah_batch[_ex],
+ * cda_extend_dah_device, cda_extend_dah_inplace_device, cda_reserve,
+ * cda_square_create, cda_square_set_create[_device], cda_sample_proofs_verify,
+ * cda_namespace_proofs_verify[_set].  The host plans name the width ("square
+ * width 2048 is not a power of two <= 1024"), cda_split_rows / cda_split_cols
+ * answer "bad row block" / "bad column block".  cda_rs_encode takes up to 1024
+ * data shards, cda_data_root up to 2048 roots per axis (CDA_ERR_UNSUPPORTED
+ * above).
+ * Repair and the fraud proofs stop at k = 512 (EDS width 1024): cda_repair*,
+ * cda_repair_batch* and cda_befp_build* answer EDS width 2048 with
+ * CDA_ERR_INVALID, "EDS width must be a power of two in [2, 1024]",
+ * cda_befp_verify / cda_befp_batch_check a batch of k = 1024 with
+ * CDA_ERR_INVALID, and cda_rs_decode 1024 data shards with
+ * CDA_ERR_UNSUPPORTED, "shard count must be a power of two <= 512". */
+
 /* Context lifecycle. device: HIP ordinal (-1 = current device). */
 int cda_ctx_create(int device, cda_ctx **out);
 int cda_ctx_destroy(cda_ctx *ctx);
@@ -234,12 +254,15 @@ int cda_extend_dah_inplace_device(cda_ctx *ctx, uint32_t k, uint32_t n, void *d_
 
 /* rsmt2d Codec.Encode (Leopard, GF(2^8) for 2*n_shards <= 256, else GF(2^16)):
  * n_codewords codewords, each n_shards data shards of shard_len bytes,
- * contiguous; parity has the same shape. n_shards a power of two. */
+ * contiguous; parity has the same shape.  n_shards <= 1024 ("more than 2048
+ * shards", CDA_ERR_UNSUPPORTED, above); a count that is no power of two is
+ * padded with zero shards up to the next one, as klauspost's encoder does. */
 int cda_rs_encode(cda_ctx *ctx, const uint8_t *data, uint32_t n_shards, uint32_t shard_len, uint32_t n_codewords,
                   uint8_t *parity);
 
 /* (*DataAvailabilityHeader).Hash: RFC-6962 root of row_roots || col_roots
- * (w roots of 90 bytes each). w == 0 gives sha256("") like Hash() on a nil DAH. */
+ * (w roots of 90 bytes each, w a power of two <= 2048). w == 0 gives
+ * sha256("") like Hash() on a nil DAH. */
 int cda_data_root(cda_ctx *ctx, const uint8_t *row_roots, const uint8_t *col_roots, uint32_t w, uint8_t *data_root);
 
 /* Details of the calling thread's last CDA_ERR_PUSH_ORDER: axis (0 row, 1

@@ -7,7 +7,9 @@ tests/golden/config4_k128.json: per square index the SHA-256 of its ODS, EDS,
 row roots, column roots and its data root, from the C oracle
 (oracle/cda_oracle.c, the CPU restatement pinned by the reference's golden
 vectors and mainnet block 408).  `--k 512 --count 2 --out
-tests/golden/k512.json` writes the same for config 3's squares 0 and 1.
+tests/golden/k512.json` writes the same for config 3's squares 0 and 1, and
+`--k 1024 --count 2 --out tests/golden/k1024.json` for the widest square the
+library accepts (tests/test_k1024.py).
 `--first 128 --count 896 --roots-only --out tests/golden/config4_k128_rest.json`
 writes the data root and root digests of the other seven ranks' squares
 (every rank's shard is then checked, not only rank 0's).

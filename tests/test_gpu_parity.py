@@ -194,17 +194,29 @@ def test_random_fixtures_on_gpu(ctx, k):
     assert dah.hash().hex() == g["data_root"]
 
 
-@pytest.mark.parametrize("k,parts", [(4, 2), (16, 4), (128, 8), (512, 8), (512, 2)])
+@pytest.mark.parametrize("k,parts", [(4, 2), (16, 4), (128, 8), (512, 8), (512, 2), (1024, 8), (1024, 2)])
 def test_split_square_loopback_on_gpu(ctx, k, parts):
     """Config 5 kernels (row block -> column block -> subtree combine) on one
-    GPU with `parts` virtual ranks: bit-exact EDS columns, roots, data root."""
+    GPU with `parts` virtual ranks: bit-exact EDS columns, roots, data root.
+    k = 1024 (the widest square; its 4 096-root data root takes the two-launch
+    form) runs square 0 against the oracle's digests in tests/golden/k1024.json."""
     import torch
     from celestia_da import dist as cdist
-    ods = coracle.random_square(k, 9)
+    ods = coracle.random_square(k, 0 if k == 1024 else 9)
     dev = torch.device("cuda", 0)
     ops = cdist.GpuSplitOps(ctx, dev)
     cols_eds, (rows, cols, root, err) = cdist.extend_dah_split_loopback(torch.from_numpy(ods).to(dev), k, parts, ops)
     torch.cuda.synchronize()
+    if k == 1024:
+        import json, os
+        with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "k1024.json")) as f:
+            want = json.load(f)["squares"]["0"]
+        sha = lambda a: hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()   # noqa: E731
+        assert int(err.item()) == 0xFFFFFFFF
+        assert sha(ods) == want["ods_sha256"] and sha(cols_eds.cpu().numpy()) == want["eds_sha256"]
+        assert sha(rows.cpu().numpy()) == want["row_roots_sha256"] and sha(cols.cpu().numpy()) == want["col_roots_sha256"]
+        assert root.cpu().numpy().tobytes().hex() == want["data_root"]
+        return
     e_eds, e_rows, e_cols, e_root = coracle.cpu_baseline(ods, 16) if k >= 64 else coracle.extend_dah(ods)
     assert int(err.item()) == 0xFFFFFFFF
     assert np.array_equal(cols_eds.cpu().numpy().reshape(-1, 512), e_eds)

@@ -61,6 +61,8 @@ ELSEWHERE = [
     (128, 512, "test_config4.py::test_config4_multi_gpu_shard_one_submission"),
     (128, 1024, "test_config4.py::test_config4_all_1024_squares_one_submission"),
     (512, 32, "test_gpu_parity.py::test_k512_batch_of_32_matches_committed_oracle_digest"),
+    (1024, 1, "test_k1024.py::test_one_square_three_entry_points"),
+    *[(1024, n, "test_k1024.py::test_inplace_batch") for n in (2, 3, 4, 5, 8)],
 ]
 
 # Classes no test can reach within the memory bound of a sweep case (at most
@@ -83,12 +85,13 @@ def test_elsewhere_names_existing_tests():
 @needs_gxx
 def test_every_plan_class_is_byte_checked():
     """SWEEP + ELSEWHERE reach every plan class of hash_plan.h (default
-    knobs, k in 1 .. 512, n in 1 .. 1024, <= 64 at k = 256, <= 32 at k = 512).
+    knobs, k in 1 .. 1024, n in 1 .. 1024, <= 64 at k = 256, <= 32 at k = 512,
+    <= 8 at k = 1024).
     An uncovered class fails with the smallest (k, n) that reaches it: the
     SWEEP row to add."""
     plans = hp.plans()
-    assert sorted({k for k, _ in plans}) == [1, 2, 4, 8, 16, 32, 64, 128, 256, 512]
-    assert len(plans) == 8 * 1024 + 64 + 32
+    assert sorted({k for k, _ in plans}) == [1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024]
+    assert len(plans) == 8 * 1024 + 64 + 32 + 8
     first = {}
     for (k, n), parts in sorted(plans.items()):
         for part in parts:

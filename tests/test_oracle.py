@@ -206,9 +206,10 @@ def _lagrange_at(F, d, xs_eval):
     return np.array(out)
 
 
-@pytest.mark.parametrize("k", [256, 512])
+@pytest.mark.parametrize("k", [256, 512, 1024])
 def test_gf16_encoder_equals_lagrange_full_size(k):
-    """The GF(2^16) restatement at the sizes the path uses (config 3, k=512),
+    """The GF(2^16) restatement at the sizes the path uses (config 3, k=512,
+    and the widest accepted square, k=1024),
     in the real lo/hi shard layout, equals Lagrange interpolation at sampled
     parity positions: no reference vector exists for GF(2^16),
     so this is its full-size intrinsic pin; the GPU is pinned to the same

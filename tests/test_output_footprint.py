@@ -95,7 +95,7 @@ WIDE_ONLY = {
     "rs8_bs_kernel": ("d_eds at k = 128", SWEEP),
     "rs8_bs_half_kernel": ("d_eds at k = 128", SWEEP),
     "rs16_bs_kernel": ("d_eds at k = 256, 512", SWEEP),
-    "rs16_lds_kernel": ("d_eds at k = 1024, a width no test runs", None),
+    "rs16_lds_kernel": ("d_eds at k = 1024", "test_k1024.py::test_one_square_three_entry_points"),
 }
 # Kernels whose every store goes to the context's or the resident square's own
 # memory (slots, digests, flags, plans, error words that the host decodes).

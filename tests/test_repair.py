@@ -78,7 +78,7 @@ def run_oracle(eds, present, rows, cols, info=None):
 
 
 # ------------------------------------------------------------------ CPU tests
-@pytest.mark.parametrize("k,L", [(1, 64), (2, 64), (4, 128), (16, 512), (128, 64), (256, 64), (512, 64)])
+@pytest.mark.parametrize("k,L", [(1, 64), (2, 64), (4, 128), (16, 512), (128, 64), (256, 64), (512, 64), (1024, 64)])
 def test_oracle_decode_round_trip(k, L):
     rng = np.random.default_rng(k)
     data = rng.integers(0, 256, (k, L), dtype=np.uint8)

@@ -3,8 +3,9 @@
 //
 //   hash_plan_host_test [NAME=VALUE ...]
 //     P k n parts p i0 m stop room : launch launch ...
-//       the plan of part p of every (k, n): k in 1, 2, 4 .. 512, n in 1 .. 1024
-//       (<= 64 at k = 256, <= 32 at k = 512).  A launch is
+//       the plan of part p of every (k, n): k in 1, 2, 4 .. 1024, n in 1 .. 1024
+//       (<= 64 at k = 256, <= 32 at k = 512, <= 8 at k = 1024: in-place arenas
+//       of 16 GiB).  A launch is
 //       kernel,n_in,sub,wide,lv,n_dig,pair,ragged,pmax,mode,threads,persistent,scratch
 //       (hash_plan.h PlanLaunch; sub is tpw for the tree top).
 //   hash_plan_host_test --top [NAME=VALUE ...]
@@ -83,8 +84,8 @@ int main(int argc, char** argv) {
                 }
         return 0;
     }
-    for (uint32_t k = 1; k <= 512; k *= 2) {
-        const uint32_t n_max = k == 512 ? 32 : k == 256 ? 64 : 1024;
+    for (uint32_t k = 1; k <= 1024; k *= 2) {
+        const uint32_t n_max = k == 1024 ? 8 : k == 512 ? 32 : k == 256 ? 64 : 1024;
         for (uint32_t n = 1; n <= n_max; n++) {
             const uint32_t parts = cda::hash_parts(k, n, K.hash_split);
             for (uint32_t p = 0; p < parts; p++) {
