@@ -79,6 +79,7 @@ EXPORTED = (
     "cda_square_set_at", "cda_square_set_dah", "cda_square_set_sample_proofs",
     "cda_square_set_namespace_plan", "cda_square_set_namespace_proofs", "cda_namespace_proofs_verify_set",
     "cda_square_set_share_proofs",
+    "cda_square_axis_halves", "cda_square_set_axis_halves", "cda_axis_halves_verify", "cda_rs_recover_data",
 )
 # cda_square_set_create source kinds (include/cda.h)
 CDA_SET_FROM_ODS = 0
@@ -363,6 +364,11 @@ def load(path: str | None = None):
         L.cda_namespace_proofs_verify_set.argtypes = [ctxp, C.c_uint32, u8p, C.c_uint32, u32p,
                                                       C.POINTER(NamespaceProofBatch), u8p]
         L.cda_square_set_share_proofs.argtypes = [vp, u32p, u32p, u32p, C.c_uint32, C.POINTER(ShareProofsOut)]
+        L.cda_square_axis_halves.argtypes = [vp, u8p, u32p, u8p, C.c_uint32, u8p]
+        L.cda_square_set_axis_halves.argtypes = [vp, u32p, u8p, u32p, u8p, C.c_uint32, u8p]
+        L.cda_axis_halves_verify.argtypes = [ctxp, C.c_uint32, u8p, u8p, C.c_uint32, u32p, u8p, u32p, u8p, C.c_uint32,
+                                             u8p, u8p, u8p]
+        L.cda_rs_recover_data.argtypes = [ctxp, u8p, C.c_uint32, C.c_uint32, C.c_uint32, u8p]
         L.cda_comm_unique_id.argtypes = [u8p]
         L.cda_comm_init.argtypes = [ctxp, C.c_int, C.c_int, u8p]
         L.cda_comm_destroy.argtypes = [ctxp]

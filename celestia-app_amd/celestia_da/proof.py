@@ -246,6 +246,13 @@ class ResidentSquare:
         from . import sampling
         return sampling.sample_proofs(self, coords, out)
 
+    def axis_halves(self, coords):
+        """Half rows / half columns of the EDS (cda_square_axis_halves): coords
+        is an (n, 3) integer array of (axis, index, side); returns an
+        axis_halves.HalfBatch."""
+        from . import axis_halves
+        return axis_halves.serve(self, coords)
+
     def namespace_proofs(self, namespaces, out=None):
         """All shares of every 29-byte namespace of `namespaces` with nmt
         ProveNamespace's proofs, absence proofs included, the rows chosen as
@@ -445,6 +452,11 @@ class ResidentSquareSet:
         """sampling.sample_proofs_set(self, coords, out)."""
         from . import sampling
         return sampling.sample_proofs_set(self, coords, out)
+
+    def axis_halves(self, coords):
+        """axis_halves.serve_set(self, coords): coords (n, 4) of (square, axis, index, side)."""
+        from . import axis_halves
+        return axis_halves.serve_set(self, coords)
 
     def namespace_plan(self, queries) -> dict:
         """cda_square_set_namespace_plan: the sizes of the answer to `queries`,

@@ -358,4 +358,102 @@ int Engine::befp_verify(const cda_befp_batch* b, uint8_t* verdict, uint8_t* rebu
     return CDA_OK;
 }
 
+// Axis halves against the DAH (celestia-node's shwap Row.Verify, EXT; restated in tests/axis_halves_ref.py):
+// half i holds cells sides[i] * k .. + k - 1 of vector (axes[i], indexes[i]) of square squares[i].  The halves
+// are ordered by side into an [n][2k][512] grid, every codeword is completed -- a left half by the encoder, a
+// right half by its mirror (launch_rs_recover: the data from the parity alone) -- the vectors are hashed as
+// erasured trees with one push-order word each (tree.hip) and the roots compared with the DAHs' by the fraud
+// proofs' compare kernel.  verdict[i] = 0 valid, 2 nmt would refuse a push (checked first), 1 the root differs.
+int Engine::axis_halves_verify(uint32_t k, const uint8_t* row_roots, const uint8_t* col_roots, uint32_t n_squares,
+                               const uint32_t* squares, const uint8_t* axes, const uint32_t* indexes,
+                               const uint8_t* sides, uint32_t n, const uint8_t* shares, uint8_t* verdict,
+                               uint8_t* vectors) {
+    CDA_TRY(check_width(k));
+    if (n == 0) return CDA_OK;
+    if (!row_roots || !axes || !indexes || !sides || !shares || !verdict) return fail(CDA_ERR_INVALID, "null buffer");
+    const std::string bad = axis_halves_check(k, n_squares, squares, axes, indexes, sides, n);
+    if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
+    if (!col_roots)
+        for (uint32_t i = 0; i < n; i++)
+            if (axes[i] == 1)
+                return fail(CDA_ERR_INVALID, "half " + std::to_string(i) + ": axis 1 (column) needs col_roots, which is NULL");
+    const uint32_t W = 2 * k;
+    const size_t half_b = (size_t)k * kShare, vec_b = 2 * half_b, dah_b = (size_t)W * kNode;
+    // grid row of half i: the left halves first, each side in the caller's order
+    uint32_t n_left = 0;
+    for (uint32_t i = 0; i < n; i++) n_left += sides[i] == 0;
+    std::vector<uint32_t> pos(n), tree_axis(n);
+    std::vector<uint8_t> want((size_t)n * kNode);
+    for (uint32_t i = 0, l = 0, r = n_left; i < n; i++) {
+        const uint32_t j = pos[i] = sides[i] ? r++ : l++;
+        tree_axis[j] = indexes[i];
+        const uint8_t* dah = (axes[i] ? col_roots : row_roots) + (squares ? squares[i] : 0u) * dah_b;
+        std::memcpy(&want[(size_t)j * kNode], dah + (size_t)indexes[i] * kNode, kNode);
+    }
+    hipStream_t s = stream_;
+    const size_t want_b = pad16((size_t)n * kNode), verd_b = pad16(n);
+    CDA_TRY(ensure(bf_in_, want_b + verd_b + (size_t)n * kNode, "hipMalloc"));
+    CDA_TRY(ensure(bf_grid_, (size_t)n * vec_b, "hipMalloc"));
+    uint8_t* in = bf_in_.as<uint8_t>();
+    uint8_t* grid = bf_grid_.as<uint8_t>();
+    uint8_t* d_verdict = in + want_b;
+    uint8_t* d_rebuilt = d_verdict + verd_b;
+    CDA_TRY(h2d(in, want.data(), (size_t)n * kNode, s, "H2D axis half roots"));
+    // a run of halves of one side lies in consecutive grid rows: one strided copy per run, each way
+    auto runs = [&](auto&& f) -> int {
+        for (uint32_t i = 0; i < n;) {
+            uint32_t e = i + 1;
+            while (e < n && sides[e] == sides[i]) e++;
+            CDA_TRY(f(i, e - i));
+            i = e;
+        }
+        return CDA_OK;
+    };
+    CDA_TRY(runs([&](uint32_t i, uint32_t cnt) {
+        return check(hipMemcpy2DAsync(grid + (size_t)pos[i] * vec_b + sides[i] * half_b, vec_b,
+                                      shares + (size_t)i * half_b, half_b, half_b, cnt, hipMemcpyHostToDevice, s),
+                     "H2D axis halves");
+    }));
+    // the RS descriptors hold 32-bit offsets: chunks of codewords below 4 GiB
+    const uint32_t max_cw = (uint32_t)(0xFFFFFFFFull / vec_b);
+    for (uint32_t side = 0; side < 2; side++) {
+        const uint32_t j_end = side ? n : n_left;
+        for (uint32_t j0 = side ? n_left : 0; j0 < j_end; j0 += max_cw) {
+            const uint32_t cnt = j_end - j0 < max_cw ? j_end - j0 : max_cw;
+            RsJob job{};
+            job.src = job.dst = grid + (size_t)j0 * vec_b;
+            job.n_seg = 1;
+            const uint32_t data = 0, parity = (uint32_t)half_b, sh = (uint32_t)kShare;
+            if (side == 0) {
+                job.seg[0] = RsSeg{cnt, data, (uint32_t)vec_b, sh, parity, (uint32_t)vec_b, sh};
+                CDA_TRY(check(launch_rs(job, k, 1, gf16(k), s), "axis halves encode"));
+            } else {
+                job.seg[0] = RsSeg{cnt, parity, (uint32_t)vec_b, sh, data, (uint32_t)vec_b, sh};
+                CDA_TRY(check(launch_rs_recover(job, k, 1, gf16(k), s), "axis halves recover"));
+            }
+        }
+    }
+    uint32_t* d_err = nullptr;
+    uint64_t root_off = 0;
+    CDA_TRY(build_trees_device(grid, kShare, W, n, k, tree_axis.data(), &d_err, s, &root_off));
+    hipLaunchKernelGGL(befp_compare_kernel, dim3((n + kBefpWaves - 1) / kBefpWaves), dim3(64 * kBefpWaves), 0, s,
+                       tr_levels_.as<uint8_t>() + root_off, d_err, in, n, d_verdict, d_rebuilt);
+    CDA_TRY(launched("axis halves compare"));
+    std::vector<uint8_t> same(n);   // the compare kernel's 3: equal and in order
+    std::vector<uint32_t> err(n);
+    CDA_TRY(d2h(same.data(), d_verdict, n, s, "D2H axis half verdicts"));
+    CDA_TRY(d2h(err.data(), d_err, (size_t)n * 4, s, "D2H axis half push order"));
+    if (vectors)
+        CDA_TRY(runs([&](uint32_t i, uint32_t cnt) {
+            return d2h(vectors + (size_t)i * vec_b, grid + (size_t)pos[i] * vec_b, (size_t)cnt * vec_b, s,
+                       "D2H axis vectors");
+        }));
+    CDA_TRY(sync(s));
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t j = pos[i];
+        verdict[i] = err[j] != push_order::kOrdered ? 2 : same[j] == 3 ? 0 : 1;
+    }
+    return CDA_OK;
+}
+
 }  // namespace cda

@@ -158,14 +158,24 @@ BS_HD void transpose8(uint32_t* r) {
     });
 }
 
+// Skew offsets of the two transforms.  Encode (INV = false): IFFT over coset
+// k (skew[K - 1 + g + d]), FFT over coset 0 (skew[g + d - 1]).  Recovery of the
+// data shards from the parity shards (INV = true) runs the inverses of the same
+// two transforms -- IFFT over coset 0, FFT over coset k -- so the butterflies
+// stay and the two offsets swap.
+template <bool INV>
+constexpr int ifft_base() { return INV ? -1 : K - 1; }
+template <bool INV>
+constexpr int fft_base() { return INV ? K - 1 : -1; }
+
 // ---- pass A: IFFT d = 1..8 over shards 16U + t (R[8t + p]) ----------------
-template <int U>
+template <int U, bool INV = false>
 BS_HD void pass_a(uint32_t* R) {
     sfor<0, 4, 1>([&](auto ld) {
         constexpr int d = 1 << decltype(ld)::value;
         sfor<0, 16, 2 * d>([&](auto gg) {
             constexpr int g = decltype(gg)::value;
-            constexpr uint32_t L = kField.skew[K - 1 + 16 * U + g + d];
+            constexpr uint32_t L = kField.skew[ifft_base<INV>() + 16 * U + g + d];
             sfor<g, g + d, 1>([&](auto ii) {
                 constexpr int i = decltype(ii)::value;
                 ifft_bfly<L>(R + 8 * i, R + 8 * (i + d));
@@ -174,13 +184,13 @@ BS_HD void pass_a(uint32_t* R) {
     });
 }
 // ---- pass C: FFT d = 8..1 over shards 16U + t ------------------------------
-template <int U>
+template <int U, bool INV = false>
 BS_HD void pass_c(uint32_t* R) {
     sfor<0, 4, 1>([&](auto ld) {
         constexpr int d = 8 >> decltype(ld)::value;
         sfor<0, 16, 2 * d>([&](auto gg) {
             constexpr int g = decltype(gg)::value;
-            constexpr uint32_t L = kField.skew[16 * U + g + d - 1];
+            constexpr uint32_t L = kField.skew[fft_base<INV>() + 16 * U + g + d];
             sfor<g, g + d, 1>([&](auto ii) {
                 constexpr int i = decltype(ii)::value;
                 fft_bfly<L>(R + 8 * i, R + 8 * (i + d));
@@ -189,12 +199,13 @@ BS_HD void pass_c(uint32_t* R) {
     });
 }
 // ---- pass B: shards 16u + t for u = 0..7 (R[8u + p]), any fixed t ----------
+template <bool INV = false>
 BS_HD void pass_b(uint32_t* R) {
     sfor<0, 3, 1>([&](auto ld) {                      // IFFT d = 16, 32, 64
         constexpr int du = 1 << decltype(ld)::value;
         sfor<0, 8, 2 * du>([&](auto gg) {
             constexpr int g = decltype(gg)::value;
-            constexpr uint32_t L = kField.skew[K - 1 + 16 * g + 16 * du];
+            constexpr uint32_t L = kField.skew[ifft_base<INV>() + 16 * g + 16 * du];
             sfor<g, g + du, 1>([&](auto ii) {
                 constexpr int i = decltype(ii)::value;
                 ifft_bfly<L>(R + 8 * i, R + 8 * (i + du));
@@ -205,7 +216,7 @@ BS_HD void pass_b(uint32_t* R) {
         constexpr int du = 4 >> decltype(ld)::value;
         sfor<0, 8, 2 * du>([&](auto gg) {
             constexpr int g = decltype(gg)::value;
-            constexpr uint32_t L = kField.skew[16 * g + 16 * du - 1];
+            constexpr uint32_t L = kField.skew[fft_base<INV>() + 16 * g + 16 * du];
             sfor<g, g + du, 1>([&](auto ii) {
                 constexpr int i = decltype(ii)::value;
                 fft_bfly<L>(R + 8 * i, R + 8 * (i + du));
@@ -221,13 +232,13 @@ BS_HD void pass_b(uint32_t* R) {
 // same constant in both lanes, so they stay wave-uniform and compile-time;
 // only shard distance 1 pairs the two lanes (the *_d1 steps below, given the
 // partner's planes P).
-template <int U>
+template <int U, bool INV = false>
 BS_HD void pass_a_hi(uint32_t* R) {   // IFFT shard distance 2, 4, 8
     sfor<0, 3, 1>([&](auto ld) {
         constexpr int dj = 1 << decltype(ld)::value;
         sfor<0, 8, 2 * dj>([&](auto gg) {
             constexpr int gj = decltype(gg)::value;
-            constexpr uint32_t L = kField.skew[K - 1 + 16 * U + 2 * gj + 2 * dj];
+            constexpr uint32_t L = kField.skew[ifft_base<INV>() + 16 * U + 2 * gj + 2 * dj];
             sfor<gj, gj + dj, 1>([&](auto ii) {
                 constexpr int i = decltype(ii)::value;
                 ifft_bfly<L>(R + 8 * i, R + 8 * (i + dj));
@@ -235,13 +246,13 @@ BS_HD void pass_a_hi(uint32_t* R) {   // IFFT shard distance 2, 4, 8
         });
     });
 }
-template <int U>
+template <int U, bool INV = false>
 BS_HD void pass_c_hi(uint32_t* R) {   // FFT shard distance 8, 4, 2
     sfor<0, 3, 1>([&](auto ld) {
         constexpr int dj = 4 >> decltype(ld)::value;
         sfor<0, 8, 2 * dj>([&](auto gg) {
             constexpr int gj = decltype(gg)::value;
-            constexpr uint32_t L = kField.skew[16 * U + 2 * gj + 2 * dj - 1];
+            constexpr uint32_t L = kField.skew[fft_base<INV>() + 16 * U + 2 * gj + 2 * dj];
             sfor<gj, gj + dj, 1>([&](auto ii) {
                 constexpr int i = decltype(ii)::value;
                 fft_bfly<L>(R + 8 * i, R + 8 * (i + dj));
@@ -283,10 +294,10 @@ BS_HD void fft_d1(uint32_t* x, const uint32_t* P, uint32_t h0) {
     if constexpr (L != kMod) mul_add<L>(x, Y);
     fence<8>(x);
 }
-template <int U>
-constexpr uint32_t ifft_d1_log(int j) { return kField.skew[K - 1 + 16 * U + 2 * j + 1]; }
-template <int U>
-constexpr uint32_t fft_d1_log(int j) { return kField.skew[16 * U + 2 * j]; }
+template <int U, bool INV = false>
+constexpr uint32_t ifft_d1_log(int j) { return kField.skew[ifft_base<INV>() + 16 * U + 2 * j + 1]; }
+template <int U, bool INV = false>
+constexpr uint32_t fft_d1_log(int j) { return kField.skew[fft_base<INV>() + 16 * U + 2 * j + 1]; }
 
 // Runs f(integral_constant<U>) for U == u as a chain of uniform if-blocks.
 template <class F>

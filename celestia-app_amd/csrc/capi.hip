@@ -988,6 +988,41 @@ int cda_befp_verify(cda_ctx* ctx, const cda_befp_batch* b, uint8_t* verdict, uin
     return guarded(ctx, [&](cda::Engine& e) -> int { return e.befp_verify(b, verdict, rebuilt_roots); });
 }
 
+int cda_square_axis_halves(cda_square* sq, const uint8_t* axes, const uint32_t* indexes, const uint8_t* sides,
+                           uint32_t n, uint8_t* shares) {
+    if (!sq) return CDA_ERR_INVALID;
+    return guarded(sq->ctx, [&](cda::Engine& e) -> int {
+        return e.axis_halves(&sq->sq, nullptr, nullptr, axes, indexes, sides, n, shares);
+    });
+}
+
+int cda_square_set_axis_halves(cda_square_set* set, const uint32_t* squares, const uint8_t* axes,
+                               const uint32_t* indexes, const uint8_t* sides, uint32_t n, uint8_t* shares) {
+    if (!set) return CDA_ERR_INVALID;
+    return guarded(set->ctx, [&](cda::Engine& e) -> int {
+        return e.axis_halves(nullptr, &set->set, squares, axes, indexes, sides, n, shares);
+    });
+}
+
+int cda_axis_halves_verify(cda_ctx* ctx, uint32_t k, const uint8_t* row_roots, const uint8_t* col_roots,
+                           uint32_t n_squares, const uint32_t* squares, const uint8_t* axes, const uint32_t* indexes,
+                           const uint8_t* sides, uint32_t n, const uint8_t* shares, uint8_t* verdict,
+                           uint8_t* vectors) {
+    return guarded(ctx, [&](cda::Engine& e) -> int {
+        return e.axis_halves_verify(k, row_roots, col_roots, n_squares, squares, axes, indexes, sides, n, shares,
+                                    verdict, vectors);
+    });
+}
+
+int cda_rs_recover_data(cda_ctx* ctx, const uint8_t* parity, uint32_t n_shards, uint32_t shard_len,
+                        uint32_t n_codewords, uint8_t* data) {
+    return guarded(ctx, [&](cda::Engine& e) -> int {
+        if (n_codewords == 0) return CDA_OK;
+        if (!parity || !data) return e.fail(CDA_ERR_INVALID, "null buffer");
+        return e.host_rs_recover(parity, n_shards, shard_len, n_codewords, data);
+    });
+}
+
 int cda_nmt_axis_roots(cda_ctx* ctx, const uint8_t* cells, uint32_t cell_len, uint32_t n_cells, uint32_t n_trees,
                        uint32_t square_size, const uint32_t* axis_index, uint8_t* roots, int32_t* status) {
     return guarded(ctx, [&](cda::Engine& e) -> int {

@@ -63,6 +63,19 @@ hipError_t launch_rs8_flat(const uint8_t* data, uint8_t* parity, uint32_t k, uin
 hipError_t launch_rs16_flat(const Gf16Dev& t, const uint8_t* data, uint8_t* parity, uint32_t k, uint32_t len,
                             uint32_t n_code, hipStream_t stream);
 
+// The mirror of the encoders: the k data shards of every codeword from its k
+// parity shards alone, by the inverses of the encoder's two transforms
+// (DESIGN.md 3.19).  The job's src names the parity half of each codeword and
+// dst the data half; the dispatch is launch_rs's, except that k = 128 always
+// runs the bitsliced kernel (two codewords per workgroup, an odd count's last
+// one alone) and k > 128 the LDS log/exp kernel.
+hipError_t launch_rs_recover(const RsJob& job, uint32_t k, uint32_t n_squares, const Gf16Dev& gf16,
+                             hipStream_t stream);
+hipError_t launch_rs8_flat_recover(const uint8_t* parity, uint8_t* data, uint32_t k, uint32_t len, uint32_t n_code,
+                                   hipStream_t stream);
+hipError_t launch_rs16_flat_recover(const Gf16Dev& t, const uint8_t* parity, uint8_t* data, uint32_t k, uint32_t len,
+                                    uint32_t n_code, hipStream_t stream);
+
 // Square phases (rsmt2d erasureExtendSquare): Q0->Q1 rows + Q0->Q2 columns
 // (with the Q0 copy), then Q2->Q3 rows.
 RsJob square_job_q0(const uint8_t* ods, uint8_t* eds, uint32_t k);

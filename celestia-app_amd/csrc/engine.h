@@ -165,6 +165,11 @@ struct GatherPiece {
 // naming the proof and the field.
 std::string befp_batch_check(const cda_befp_batch* b);
 
+// proof.hip: the first bad coordinate of a batch of axis halves, host only: "" or its text, naming the half and
+// the field (squares == NULL: one square).
+std::string axis_halves_check(uint32_t k, uint32_t n_squares, const uint32_t* squares, const uint8_t* axes,
+                              const uint32_t* indexes, const uint8_t* sides, uint32_t n);
+
 // repair.hip: squares per verification chunk of a batch repair of width w (the fixed caps of include/cda.h).
 uint32_t repair_batch_chunk(uint32_t w);
 
@@ -451,6 +456,21 @@ class Engine {
                    const uint8_t* row_roots, const uint8_t* col_roots, uint32_t* n_out, uint32_t* positions,
                    uint8_t* shares, uint8_t* nmt_nodes);
     int befp_verify(const cda_befp_batch* b, uint8_t* verdict, uint8_t* rebuilt_roots);
+
+    // Axis halves (include/cda.h "Axis halves").  axis_halves (proof.hip): half i = cells sides[i] * k .. + k - 1
+    // of row or column indexes[i] of the square sq, or of member squares[i] of the set (sq == NULL); one gather
+    // launch, one copy back.  axis_halves_verify (befp.hip): each half completed to its vector (the encoder for
+    // a left half, launch_rs_recover for a right one), hashed as an erasured tree and compared with root
+    // (squares[i], axes[i], indexes[i]) of the DAHs; verdict 0 valid, 2 push order, 1 root; vectors optional.
+    int axis_halves(ResidentSquare* sq, ResidentSquareSet* set, const uint32_t* squares, const uint8_t* axes,
+                    const uint32_t* indexes, const uint8_t* sides, uint32_t n, uint8_t* shares);
+    int axis_halves_verify(uint32_t k, const uint8_t* row_roots, const uint8_t* col_roots, uint32_t n_squares,
+                           const uint32_t* squares, const uint8_t* axes, const uint32_t* indexes, const uint8_t* sides,
+                           uint32_t n, const uint8_t* shares, uint8_t* verdict, uint8_t* vectors);
+    // The mirror of enqueue_rs / host_rs: the k data shards of n codewords from their k parity shards alone.
+    int enqueue_rs_recover(const uint8_t* d_parity, uint8_t* d_data, uint32_t k, uint32_t len, uint32_t n,
+                           hipStream_t s);
+    int host_rs_recover(const uint8_t* parity, uint32_t k, uint32_t len, uint32_t n, uint8_t* data);
 
     // Stage timing with HIP events on the launch stream (bench / profiling).
     enum Stage { kStageRsQ0 = 0, kStageRsQ3, kStageOrder, kStageLeaves, kStageLevels, kStageDataRoot,

@@ -869,6 +869,49 @@ int Engine::enqueue_rs(const uint8_t* d_data, uint8_t* d_parity, uint32_t k, uin
     return check(launch_rs16_flat(gf16(k), d_data, d_parity, k, len, n, s), "rs16 flat");
 }
 
+// The mirror of enqueue_rs (cda_rs_recover_data): n codewords' k data shards from their k parity shards, by the
+// recovery instantiations of the encoder kernels.  512-byte shards go through the job form, so that k = 128
+// runs the bitsliced kernel as it does for the halves of a square; other lengths through the flat kernels.
+int Engine::enqueue_rs_recover(const uint8_t* d_parity, uint8_t* d_data, uint32_t k, uint32_t len, uint32_t n,
+                               hipStream_t s) {
+    if (!is_pow2(k) || k > 1024) return fail(CDA_ERR_UNSUPPORTED, "shard count must be a power of two <= 1024");
+    if (len % 64) {
+        char buf[96];
+        snprintf(buf, sizeof buf, "chunkSize %u must be a multiple of 64 bytes", len);
+        return fail(CDA_ERR_CHUNK_SIZE, buf);
+    }
+    if (len == 0) return CDA_OK;
+    if (k == 1)
+        return check(hipMemcpyAsync(d_data, d_parity, (size_t)len * n, hipMemcpyDeviceToDevice, s), "copy");
+    if (len == (uint32_t)kShare) {
+        const size_t cw_b = (size_t)k * kShare;
+        const uint32_t max_cw = (uint32_t)(0xFFFFFFFFull / cw_b);   // the descriptors hold 32-bit offsets
+        for (uint32_t c0 = 0; c0 < n; c0 += max_cw) {
+            const uint32_t cnt = n - c0 < max_cw ? n - c0 : max_cw;
+            RsJob job{};
+            job.src = d_parity + (size_t)c0 * cw_b;
+            job.dst = d_data + (size_t)c0 * cw_b;
+            job.n_seg = 1;
+            job.seg[0] = RsSeg{cnt, 0, (uint32_t)cw_b, (uint32_t)kShare, 0, (uint32_t)cw_b, (uint32_t)kShare};
+            CDA_TRY(check(launch_rs_recover(job, k, 1, gf16(k), s), "rs recover"));
+        }
+        return CDA_OK;
+    }
+    if (k <= 128) return check(launch_rs8_flat_recover(d_parity, d_data, k, len, n, s), "rs8 flat recover");
+    return check(launch_rs16_flat_recover(gf16(k), d_parity, d_data, k, len, n, s), "rs16 flat recover");
+}
+
+int Engine::host_rs_recover(const uint8_t* parity, uint32_t k, uint32_t len, uint32_t n, uint8_t* data) {
+    const size_t b = (size_t)n * k * len;
+    CDA_TRY(ensure(h_ods_, b, "hipMalloc"));
+    CDA_TRY(ensure(h_eds_, b, "hipMalloc"));
+    hipStream_t s = stream_;
+    CDA_TRY(h2d(h_eds_.ptr, parity, b, s, "H2D"));
+    CDA_TRY(enqueue_rs_recover(h_eds_.as<uint8_t>(), h_ods_.as<uint8_t>(), k, len, n, s));
+    CDA_TRY(d2h(data, h_ods_.ptr, b, s, "D2H"));
+    return sync(s);
+}
+
 // cda_push_order_detail_at: the decoded push-order word of square sq of the
 // last device batch, once that batch's GPU work (the call's end event) is done.
 int Engine::device_push_order_detail(uint32_t sq, int32_t* axis, uint32_t* index, uint32_t* pos) {

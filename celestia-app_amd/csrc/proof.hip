@@ -224,6 +224,62 @@ int Engine::square_gather_device(ResidentSquare* sq, const std::vector<GatherPie
     return wait ? sync(s) : CDA_OK;
 }
 
+// The first bad coordinate of a batch of axis halves ("" if none): the text names the half and the field.
+// n_squares: the members of the set or the DAHs of the verifier (squares == NULL: one square, nothing to check).
+std::string axis_halves_check(uint32_t k, uint32_t n_squares, const uint32_t* squares, const uint8_t* axes,
+                              const uint32_t* indexes, const uint8_t* sides, uint32_t n) {
+    const uint32_t W = 2 * k;
+    for (uint32_t i = 0; i < n; i++) {
+        const std::string at = "half " + std::to_string(i) + ": ";
+        if (squares && squares[i] >= n_squares)
+            return at + "square " + std::to_string(squares[i]) + " is not below the " + std::to_string(n_squares) +
+                   " squares";
+        if (axes[i] > 1) return at + "axis " + std::to_string(axes[i]) + " is neither 0 (row) nor 1 (column)";
+        if (indexes[i] >= W)
+            return at + "index " + std::to_string(indexes[i]) + " is not below the EDS width " + std::to_string(W);
+        if (sides[i] > 1) return at + "side " + std::to_string(sides[i]) + " is neither 0 (left) nor 1 (right)";
+    }
+    return "";
+}
+
+// Axis halves of one resident square (sq) or of the members squares[i] of a set (sq == NULL): half i is the k
+// cells side * k .. side * k + k - 1 of row or column `index`, k * 512 bytes of the output.  A row half is one
+// contiguous piece of the EDS, a column half k pieces of one share; one gather launch, one copy back.  The
+// piece table rides behind the output in the scratch buffer.
+int Engine::axis_halves(ResidentSquare* sq, ResidentSquareSet* set, const uint32_t* squares, const uint8_t* axes,
+                        const uint32_t* indexes, const uint8_t* sides, uint32_t n, uint8_t* shares) {
+    if (n == 0) return CDA_OK;
+    if ((set && !sq && !squares) || !axes || !indexes || !sides || !shares) return fail(CDA_ERR_INVALID, "null buffer");
+    const uint32_t k = sq ? sq->k : set->k, W = 2 * k;
+    const std::string bad = axis_halves_check(k, sq ? 0 : set->n, sq ? nullptr : squares, axes, indexes, sides, n);
+    if (!bad.empty()) return fail(CDA_ERR_INVALID, bad);
+    const uint64_t half_b = (uint64_t)k * kShare;
+    std::vector<GatherPiece> pieces;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint8_t* eds = sq ? sq->eds.as<uint8_t>() : set->eds.as<uint8_t>() + (uint64_t)squares[i] * set->eds_sq;
+        const uint64_t first = (uint64_t)sides[i] * k, dst = i * half_b;
+        if (axes[i] == 0) {
+            pieces.push_back(GatherPiece{eds + ((uint64_t)indexes[i] * W + first) * kShare, dst, (uint32_t)half_b});
+        } else {
+            for (uint32_t j = 0; j < k; j++)
+                pieces.push_back(GatherPiece{eds + ((first + j) * W + indexes[i]) * kShare, dst + (uint64_t)j * kShare,
+                                             (uint32_t)kShare});
+        }
+    }
+    const size_t out_b = (size_t)(n * half_b), table_b = pieces.size() * sizeof(GatherPiece);
+    DevBuf& scratch = sq ? sq->scratch : set->scratch;
+    hipStream_t s = stream_;
+    CDA_TRY(ensure(scratch, out_b + table_b, "hipMalloc"));
+    uint8_t* scr = scratch.as<uint8_t>();
+    GatherPiece* table = reinterpret_cast<GatherPiece*>(scr + out_b);   // out_b is a multiple of 512
+    CDA_TRY(h2d(table, pieces.data(), table_b, s, "H2D pieces"));
+    hipLaunchKernelGGL(gather_kernel, dim3(((uint32_t)pieces.size() + 3) / 4), dim3(256), 0, s, table,
+                       (uint32_t)pieces.size(), scr);
+    CDA_TRY(launched("axis halves"));
+    CDA_TRY(d2h(shares, scr, out_b, s, "D2H axis halves"));
+    return sync(s);   // `pieces` is pageable and the output is the caller's: complete before returning
+}
+
 int Engine::regions_out(const OutRegions& out, const uint8_t* scratch, bool one_copy, hipStream_t s,
                         const char* what) {
     if (!one_copy) {

@@ -32,6 +32,9 @@ __device__ __forceinline__ uint32_t mul16(const uint16_t* __restrict__ lg, const
 }
 
 // One 64-byte block column of one codeword.  src/dst: shard i at base + i*stride.
+// INV: the data shards from the parity shards -- the same two transforms with
+// their skew offsets swapped; src is then the parity half.
+template <bool INV>
 __device__ void encode_block_column(const Gf16Dev& t, uint16_t* sym, uint32_t k, const uint8_t* src, size_t src_stride,
                                     uint8_t* dst, size_t dst_stride, uint8_t* copy, size_t copy_stride) {
     const uint32_t tid = threadIdx.x, nt = blockDim.x;
@@ -52,7 +55,7 @@ __device__ void encode_block_column(const Gf16Dev& t, uint16_t* sym, uint32_t k,
         for (uint32_t w = tid; w < items; w += nt) {
             const uint32_t p = w >> 5, s = w & 31;
             const uint32_t g = (p / d) * 2 * d, i = g + (p % d);
-            const uint32_t L = t.skew[m - 1 + g + d];
+            const uint32_t L = t.skew[(INV ? 0 : m) + g + d - 1];
             uint32_t x = sym[i * 32 + s], y = sym[(i + d) * 32 + s];
             y ^= x;
             if (L != kMod16) x ^= mul16(t.log, t.exp, y, L);
@@ -65,7 +68,7 @@ __device__ void encode_block_column(const Gf16Dev& t, uint16_t* sym, uint32_t k,
         for (uint32_t w = tid; w < items; w += nt) {
             const uint32_t p = w >> 5, s = w & 31;
             const uint32_t g = (p / d) * 2 * d, i = g + (p % d);
-            const uint32_t L = t.skew[g + d - 1];
+            const uint32_t L = t.skew[(INV ? m : 0) + g + d - 1];
             uint32_t x = sym[i * 32 + s], y = sym[(i + d) * 32 + s];
             if (L != kMod16) x ^= mul16(t.log, t.exp, y, L);
             y ^= x;
@@ -85,6 +88,7 @@ __device__ void encode_block_column(const Gf16Dev& t, uint16_t* sym, uint32_t k,
     }
 }
 
+template <bool INV = false>
 __global__ __launch_bounds__(256) void rs16_lds_kernel(Gf16Dev t, const RsJob job, uint32_t k) {
     rs_err_init(job);
     extern __shared__ __attribute__((aligned(16))) uint16_t sym[];
@@ -96,18 +100,19 @@ __global__ __launch_bounds__(256) void rs16_lds_kernel(Gf16Dev t, const RsJob jo
     const uint8_t* src = job.src + blockIdx.y * job.src_sq;
     uint8_t* dst = job.dst + blockIdx.y * job.dst_sq;
     const size_t off = (size_t)blk * 64;
-    encode_block_column(t, sym, k, src + (size_t)g.src_off + (size_t)c * g.src_cw + off, g.src_sh,
+    encode_block_column<INV>(t, sym, k, src + (size_t)g.src_off + (size_t)c * g.src_cw + off, g.src_sh,
                         dst + (size_t)g.dst_off + (size_t)c * g.dst_cw + off, g.dst_sh,
                         g.cpy_off == kNoCopy ? nullptr : dst + (size_t)g.cpy_off + (size_t)c * g.cpy_cw + off,
                         g.cpy_sh);
 }
 
+template <bool INV = false>
 __global__ __launch_bounds__(256) void rs16_flat_kernel(Gf16Dev t, const uint8_t* __restrict__ data,
                                                        uint8_t* __restrict__ parity, uint32_t k, uint32_t len) {
     extern __shared__ __attribute__((aligned(16))) uint16_t sym[];
     const size_t c = blockIdx.y;
     const size_t off = (size_t)blockIdx.x * 64;
-    encode_block_column(t, sym, k, data + c * (size_t)k * len + off, len, parity + c * (size_t)k * len + off, len,
+    encode_block_column<INV>(t, sym, k, data + c * (size_t)k * len + off, len, parity + c * (size_t)k * len + off, len,
                         nullptr, 0);
 }
 
@@ -122,7 +127,31 @@ hipError_t launch_rs(const RsJob& j, uint32_t k, uint32_t n, const Gf16Dev& t, h
     const size_t lds = (size_t)k * 64;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     const uint32_t ncw = j.seg[0].n_cw + (j.n_seg > 1 ? j.seg[1].n_cw : 0);
-    hipLaunchKernelGGL(rs16_lds_kernel, dim3(ncw * 8, n), dim3(256), lds, s, t, j, k);
+    hipLaunchKernelGGL(rs16_lds_kernel<false>, dim3(ncw * 8, n), dim3(256), lds, s, t, j, k);
+    return hipGetLastError();
+}
+
+hipError_t launch_rs8_job_recover(const RsJob& j, uint32_t k, uint32_t n, hipStream_t s);
+
+// launch_rs's mirror: k <= 128 the GF(2^8) recovery kernels (k = 128 bitsliced), above it the LDS log/exp
+// kernel with k * 64 B of LDS (k = 256, 512, 1024: 16, 32, 64 KiB); a bitsliced GF(2^16) recovery does not exist.
+hipError_t launch_rs_recover(const RsJob& j, uint32_t k, uint32_t n, const Gf16Dev& t, hipStream_t s) {
+    if (k == 0 || (k & (k - 1))) return hipErrorInvalidValue;
+    if (k <= 128) return launch_rs8_job_recover(j, k, n, s);
+    const size_t lds = (size_t)k * 64;
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    const uint32_t ncw = j.seg[0].n_cw + (j.n_seg > 1 ? j.seg[1].n_cw : 0);
+    hipLaunchKernelGGL(rs16_lds_kernel<true>, dim3(ncw * 8, n), dim3(256), lds, s, t, j, k);
+    return hipGetLastError();
+}
+
+hipError_t launch_rs16_flat_recover(const Gf16Dev& t, const uint8_t* p, uint8_t* d, uint32_t k, uint32_t len,
+                                    uint32_t n, hipStream_t s) {
+    if (k < 2 || (k & (k - 1)) || len % 64) return hipErrorInvalidValue;
+    const size_t lds = (size_t)k * 64;
+    if (lds > 64 * 1024) return hipErrorInvalidValue;
+    dim3 grid(len / 64, n);
+    hipLaunchKernelGGL(rs16_flat_kernel<true>, grid, dim3(256), lds, s, t, p, d, k, len);
     return hipGetLastError();
 }
 
@@ -132,7 +161,7 @@ hipError_t launch_rs16_flat(const Gf16Dev& t, const uint8_t* d, uint8_t* p, uint
     const size_t lds = (size_t)k * 64;
     if (lds > 64 * 1024) return hipErrorInvalidValue;
     dim3 grid(len / 64, n);
-    hipLaunchKernelGGL(rs16_flat_kernel, grid, dim3(256), lds, s, t, d, p, k, len);
+    hipLaunchKernelGGL(rs16_flat_kernel<false>, grid, dim3(256), lds, s, t, d, p, k, len);
     return hipGetLastError();
 }
 

@@ -58,18 +58,21 @@ __device__ __forceinline__ uint32_t mul_add(uint32_t x, uint32_t y) {
     return xor3(x, xor3(p0, p1, p2), p3);
 }
 
-template <int M, int D, int G>
+// INV (recovery of the data shards from the parity shards):
+// the same butterflies with the two skew offsets swapped -- the IFFT over
+// coset 0 undoes the encoder's FFT, the FFT over coset k its IFFT.
+template <bool INV, int M, int D, int G>
 __device__ __forceinline__ void ifft_group(uint32_t (&v)[M]) {
-    constexpr uint32_t L = kF8.skew[M - 1 + G + D];
+    constexpr uint32_t L = kF8.skew[(INV ? -1 : M - 1) + G + D];
 #pragma unroll
     for (int i = G; i < G + D; i++) {
         v[i + D] ^= v[i];
         if constexpr (L != kMod8) v[i] = mul_add<L>(v[i], v[i + D]);
     }
 }
-template <int M, int D, int G>
+template <bool INV, int M, int D, int G>
 __device__ __forceinline__ void fft_group(uint32_t (&v)[M]) {
-    constexpr uint32_t L = kF8.skew[G + D - 1];
+    constexpr uint32_t L = kF8.skew[(INV ? M - 1 : -1) + G + D];
 #pragma unroll
     for (int i = G; i < G + D; i++) {
         if constexpr (L != kMod8) v[i] = mul_add<L>(v[i], v[i + D]);
@@ -77,40 +80,40 @@ __device__ __forceinline__ void fft_group(uint32_t (&v)[M]) {
     }
 }
 
-template <int M, int D, int G = 0>
+template <bool INV, int M, int D, int G = 0>
 __device__ __forceinline__ void ifft_layer(uint32_t (&v)[M]) {
     if constexpr (G < M) {
-        ifft_group<M, D, G>(v);
-        ifft_layer<M, D, G + 2 * D>(v);
+        ifft_group<INV, M, D, G>(v);
+        ifft_layer<INV, M, D, G + 2 * D>(v);
     }
 }
-template <int M, int D, int G = 0>
+template <bool INV, int M, int D, int G = 0>
 __device__ __forceinline__ void fft_layer(uint32_t (&v)[M]) {
     if constexpr (G < M) {
-        fft_group<M, D, G>(v);
-        fft_layer<M, D, G + 2 * D>(v);
+        fft_group<INV, M, D, G>(v);
+        fft_layer<INV, M, D, G + 2 * D>(v);
     }
 }
-template <int M, int D = 1>
+template <bool INV, int M, int D = 1>
 __device__ __forceinline__ void ifft_all(uint32_t (&v)[M]) {
     if constexpr (D < M) {
-        ifft_layer<M, D>(v);
-        ifft_all<M, 2 * D>(v);
+        ifft_layer<INV, M, D>(v);
+        ifft_all<INV, M, 2 * D>(v);
     }
 }
-template <int M, int D = M / 2>
+template <bool INV, int M, int D = M / 2>
 __device__ __forceinline__ void fft_all(uint32_t (&v)[M]) {
     if constexpr (D >= 1) {
-        fft_layer<M, D>(v);
-        fft_all<M, D / 2>(v);
+        fft_layer<INV, M, D>(v);
+        fft_all<INV, M, D / 2>(v);
     }
 }
 
-template <int M>
+template <bool INV, int M>
 __device__ __forceinline__ void encode_regs(uint32_t (&v)[M]) {
     if constexpr (M > 1) {
-        ifft_all<M>(v);
-        fft_all<M>(v);
+        ifft_all<INV, M>(v);
+        fft_all<INV, M>(v);
     }
 }
 
@@ -137,7 +140,7 @@ __device__ __forceinline__ SegSel select_seg(const RsJob& j, uint32_t cw) {
     return r;
 }
 
-template <int K>
+template <int K, bool INV = false>
 __global__ __launch_bounds__(128, waves_per_simd<K>()) void rs8_job_kernel(const RsJob job) {
     rs_err_init(job);
     const SegSel q = select_seg(job, blockIdx.x);
@@ -152,14 +155,14 @@ __global__ __launch_bounds__(128, waves_per_simd<K>()) void rs8_job_kernel(const
 #pragma unroll
         for (int i = 0; i < K; i++) *reinterpret_cast<uint32_t*>(dst + (q.c0 + i * q.cs + lane4)) = v[i];
     }
-    encode_regs<K>(v);
+    encode_regs<INV, K>(v);
 #pragma unroll
     for (int i = 0; i < K; i++) *reinterpret_cast<uint32_t*>(dst + (q.d0 + i * q.ds + lane4)) = v[i];
 }
 
 // Flat codewords: codeword c = data[c*K*len ...], shards of len bytes.
 // Grid: (len/512 rounded up, n_code); 128 lanes x 4 B per block.
-template <int K>
+template <int K, bool INV = false>
 __global__ __launch_bounds__(128, waves_per_simd<K>()) void rs8_flat_kernel(const uint8_t* __restrict__ data, uint8_t* __restrict__ parity,
                                                       uint32_t len) {
     const size_t c = blockIdx.y;
@@ -170,21 +173,21 @@ __global__ __launch_bounds__(128, waves_per_simd<K>()) void rs8_flat_kernel(cons
     uint32_t v[K];
 #pragma unroll
     for (int i = 0; i < K; i++) v[i] = *reinterpret_cast<const uint32_t*>(src + (size_t)i * len);
-    encode_regs<K>(v);
+    encode_regs<INV, K>(v);
 #pragma unroll
     for (int i = 0; i < K; i++) *reinterpret_cast<uint32_t*>(dst + (size_t)i * len) = v[i];
 }
 
-template <int K>
+template <int K, bool INV = false>
 hipError_t launch_job(const RsJob& j, uint32_t n, hipStream_t s) {
     const uint32_t ncw = j.seg[0].n_cw + (j.n_seg > 1 ? j.seg[1].n_cw : 0);
-    hipLaunchKernelGGL(rs8_job_kernel<K>, dim3(ncw, n), dim3(128), 0, s, j);
+    hipLaunchKernelGGL((rs8_job_kernel<K, INV>), dim3(ncw, n), dim3(128), 0, s, j);
     return hipGetLastError();
 }
-template <int K>
+template <int K, bool INV = false>
 hipError_t launch_fl(const uint8_t* d, uint8_t* p, uint32_t len, uint32_t n, hipStream_t s) {
     dim3 grid((len / 4 + 127) / 128, n);
-    hipLaunchKernelGGL(rs8_flat_kernel<K>, grid, dim3(128), 0, s, d, p, len);
+    hipLaunchKernelGGL((rs8_flat_kernel<K, INV>), grid, dim3(128), 0, s, d, p, len);
     return hipGetLastError();
 }
 
@@ -208,6 +211,27 @@ hipError_t launch_rs8_job(const RsJob& j, uint32_t k, uint32_t n, hipStream_t s)
         case 32: return launch_job<32>(j, n, s);
         case 64: return launch_job<64>(j, n, s);
         case 128: return launch_job<128>(j, n, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_rs8_bs_recover(const RsJob& j, uint32_t n, hipStream_t s);
+
+// The data shards of every codeword of the job from its parity shards: src
+// names the parity half, dst the data half.  k = 128: the bitsliced kernel
+// (CDA_RS8_BYTEFORM=1: this file's, for A/B measurement).
+hipError_t launch_rs8_job_recover(const RsJob& j, uint32_t k, uint32_t n, hipStream_t s) {
+    static const bool byteform = test_knob("CDA_RS8_BYTEFORM") && atoi(test_knob("CDA_RS8_BYTEFORM"));
+    if (k == 128 && !byteform) return launch_rs8_bs_recover(j, n, s);
+    switch (k) {
+        case 1: return launch_job<1, true>(j, n, s);
+        case 2: return launch_job<2, true>(j, n, s);
+        case 4: return launch_job<4, true>(j, n, s);
+        case 8: return launch_job<8, true>(j, n, s);
+        case 16: return launch_job<16, true>(j, n, s);
+        case 32: return launch_job<32, true>(j, n, s);
+        case 64: return launch_job<64, true>(j, n, s);
+        case 128: return launch_job<128, true>(j, n, s);
         default: return hipErrorInvalidValue;
     }
 }
@@ -265,6 +289,21 @@ hipError_t launch_rs8_flat(const uint8_t* d, uint8_t* p, uint32_t k, uint32_t le
         case 32: return launch_fl<32>(d, p, len, n, s);
         case 64: return launch_fl<64>(d, p, len, n, s);
         case 128: return launch_fl<128>(d, p, len, n, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_rs8_flat_recover(const uint8_t* p, uint8_t* d, uint32_t k, uint32_t len, uint32_t n,
+                                   hipStream_t s) {
+    switch (k) {
+        case 1: return launch_fl<1, true>(p, d, len, n, s);
+        case 2: return launch_fl<2, true>(p, d, len, n, s);
+        case 4: return launch_fl<4, true>(p, d, len, n, s);
+        case 8: return launch_fl<8, true>(p, d, len, n, s);
+        case 16: return launch_fl<16, true>(p, d, len, n, s);
+        case 32: return launch_fl<32, true>(p, d, len, n, s);
+        case 64: return launch_fl<64, true>(p, d, len, n, s);
+        case 128: return launch_fl<128, true>(p, d, len, n, s);
         default: return hipErrorInvalidValue;
     }
 }

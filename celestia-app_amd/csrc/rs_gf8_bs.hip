@@ -172,7 +172,10 @@ __device__ __forceinline__ uint32_t swap_h(uint32_t v) {   // lane l <- its shar
 // The codewords of one workgroup (every MODE): lane codeword cwb + lcw of
 // square sq, lane columns col..col+15 and col+kHi..col+kHi+15 (cwb uniform:
 // segments hold whole workgroups).  E: the exchange buffer (64 KiB of LDS).
-template <int MODE>
+// INV: the data shards from the parity shards (bitslice8.h ifft_base /
+// fft_base: the same passes with the two skew offsets swapped); src then
+// names the parity half of a codeword and dst its data half.
+template <int MODE, bool INV = false>
 __device__ __forceinline__ void rs8_half_body(const RsJob& job, uint32_t* E, uint32_t sq, uint32_t cwb, uint32_t lcw,
                                               uint32_t col) {
     constexpr bool ONE = MODE == 1;
@@ -236,9 +239,9 @@ __device__ __forceinline__ void rs8_half_body(const RsJob& job, uint32_t* E, uin
             uint32_t P[8];
 #pragma unroll
             for (int p = 0; p < 8; p++) P[p] = swap_h<MODE>(R[8 * j + p]);
-            ifft_d1<ifft_d1_log<UU>(j)>(R + 8 * j, P, h0);
+            ifft_d1<ifft_d1_log<UU, INV>(j)>(R + 8 * j, P, h0);
         });
-        pass_a_hi<UU>(R);
+        pass_a_hi<UU, INV>(R);
     });
     // ---- A -> B: register j of wave u -> register u of wave j; round r moves
     // planes 4r..4r+3 (slot [a][b] = pass-A wave b's register a)
@@ -256,7 +259,7 @@ __device__ __forceinline__ void rs8_half_body(const RsJob& job, uint32_t* E, uin
             for (int pp = 0; pp < 4; pp++) R[8 * uu + 4 * r + pp] = E[((w * 8 + uu) * 4 + pp) * 64 + l];
     }
     // ---- pass B: shards 16u + 2w + h of every u (R[8u + p])
-    pass_b(R);
+    pass_b<INV>(R);
     // ---- B -> A
 #pragma unroll
     for (int r = 0; r < 2; r++) {
@@ -275,13 +278,13 @@ __device__ __forceinline__ void rs8_half_body(const RsJob& job, uint32_t* E, uin
     // ---- pass C: FFT shard distance 8, 4, 2, then 1 across the lane pair
     with_u_chain(ud, [&](auto U) {
         constexpr int UU = decltype(U)::value;
-        pass_c_hi<UU>(R);
+        pass_c_hi<UU, INV>(R);
         sfor<0, 8, 1>([&](auto jj) {
             constexpr int j = decltype(jj)::value;
             uint32_t P[8];
 #pragma unroll
             for (int p = 0; p < 8; p++) P[p] = swap_h<MODE>(R[8 * j + p]);
-            fft_d1<fft_d1_log<UU>(j)>(R + 8 * j, P, h0);
+            fft_d1<fft_d1_log<UU, INV>(j)>(R + 8 * j, P, h0);
         });
     });
 #pragma unroll
@@ -296,7 +299,7 @@ __device__ __forceinline__ void rs8_half_body(const RsJob& job, uint32_t* E, uin
     }
 }
 
-template <int MODE>
+template <int MODE, bool INV = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void rs8_bs_half_kernel(const RsJob job,
                                                                                                    uint32_t nsq) {
     constexpr bool ONE = MODE == 1;
@@ -325,7 +328,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void r
         lcw = ONE ? 0u : l >> 5;
         col = 16 * (l & 15);
     }
-    rs8_half_body<MODE>(job, E, sq, cwb, lcw, col);
+    rs8_half_body<MODE, INV>(job, E, sq, cwb, lcw, col);
 }
 
 }  // namespace
@@ -401,6 +404,33 @@ hipError_t launch_rs8_bs(const RsJob& j, uint32_t n, hipStream_t s) {
     }
     hipLaunchKernelGGL(rs8_bs_kernel, dim3(ncw / 4, n), dim3(512), kLdsBytes, s, j);
     return hipGetLastError();
+}
+
+// Recovery at k = 128, the INV instantiations of the half-footprint kernel:
+// the even part of every segment two codewords per workgroup (MODE 0), the
+// last codeword of an odd count one per workgroup (MODE 1).
+hipError_t launch_rs8_bs_recover(const RsJob& j, uint32_t n, hipStream_t s) {
+    for (uint32_t g = 0; g < j.n_seg; g++) {
+        RsJob part = j;
+        part.n_seg = 1;
+        part.seg[0] = j.seg[g];
+        RsSeg& q = part.seg[0];
+        const uint32_t even = q.n_cw & ~1u, odd = q.n_cw & 1u;
+        if (even) {
+            q.n_cw = even;
+            hipLaunchKernelGGL((rs8_bs_half_kernel<0, true>), dim3(even / 2, n), dim3(512), kHalfLdsBytes, s, part, n);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        }
+        if (odd) {
+            q.n_cw = 1;
+            q.src_off += even * q.src_cw;
+            q.dst_off += even * q.dst_cw;
+            if (q.cpy_off != kNoCopy) q.cpy_off += even * q.cpy_cw;
+            hipLaunchKernelGGL((rs8_bs_half_kernel<1, true>), dim3(1, n), dim3(512), kHalfLdsBytes, s, part, n);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
 }
 
 }  // namespace cda

@@ -150,10 +150,10 @@ typedef struct cda_ctx cda_ctx;
  * cda_dah_from_eds, cda_extend_dah, cda_extend_dah_batch[_ex],
  * cda_extend_dah_device, cda_extend_dah_inplace_device, cda_reserve,
  * cda_square_create, cda_square_set_create[_device], cda_sample_proofs_verify,
- * cda_namespace_proofs_verify[_set].  The host plans name the width ("square
+ * cda_namespace_proofs_verify[_set], cda_axis_halves_verify.  The host plans name the width ("square
  * width 2048 is not a power of two <= 1024"), cda_split_rows / cda_split_cols
- * answer "bad row block" / "bad column block".  cda_rs_encode takes up to 1024
- * data shards, cda_data_root up to 2048 roots per axis (CDA_ERR_UNSUPPORTED
+ * answer "bad row block" / "bad column block".  cda_rs_encode and
+ * cda_rs_recover_data take up to 1024 data shards, cda_data_root up to 2048 roots per axis (CDA_ERR_UNSUPPORTED
  * above).
  * Repair and the fraud proofs stop at k = 512 (EDS width 1024): cda_repair*,
  * cda_repair_batch* and cda_befp_build* answer EDS width 2048 with
@@ -1118,6 +1118,62 @@ int cda_befp_batch_check(const cda_befp_batch *b);
  * the push-order check; zeros for proofs with verdict 1 or 2.  Host buffers;
  * at most two synchronisations; n_proofs == 0 returns CDA_OK. */
 int cda_befp_verify(cda_ctx *ctx, const cda_befp_batch *b, uint8_t *verdict, uint8_t *rebuilt_roots);
+
+/* ---- Axis halves: serve and check half rows and half columns ----------------------
+ * The unit a full node rebuilds a square from (celestia-node's shwap Row and
+ * the eds store's AxisHalf, EXT): k consecutive cells of one row or column of
+ * the EDS.  Half i is named by axes[i] (0 = row, 1 = column), indexes[i]
+ * (0 .. 2k-1, parity rows and columns included) and sides[i]: side 0 = cells
+ * 0 .. k-1 of the vector, side 1 = cells k .. 2k-1.  Its k shares are
+ * shares[i*k*512 ..], in vector order.  All pointers are host pointers;
+ * n == 0 returns CDA_OK; duplicates are allowed.
+ *
+ * Refused with CDA_ERR_INVALID before anything is written, the text naming
+ * the half and the field ("half 3: index 9 is not below the EDS width 8"): an
+ * index >= 2k, an axis or a side above 1, squares[i] not below the set's /
+ * the DAHs' count, and for the verifier a NULL col_roots where a half has
+ * axis 1.
+ *
+ * cda_square_axis_halves / cda_square_set_axis_halves: n halves of a resident
+ * square, or of the members squares[i] of a set, in one gather launch and one
+ * copy back (a row half is one piece of k*512 bytes, a column half k pieces).
+ *
+ * cda_axis_halves_verify: Row.Verify for a batch, left and right halves
+ * mixed.  Every half is completed to its vector of 2k cells -- a left half by
+ * the encoder, a right half by its mirror, which computes the k data shards
+ * from the k parity shards alone -- the vector is hashed as the wrapper's
+ * erasured tree (index < k: cells < k keep their namespace, the rest take the
+ * parity namespace; index >= k: every cell the parity namespace) and its root
+ * compared with root (squares[i], axes[i], indexes[i]) of the DAHs:
+ * row_roots / col_roots hold n_squares * 2k roots of 90 bytes, square by
+ * square; squares == NULL: one DAH, every half against it.  col_roots may be
+ * NULL when no half has axis 1.  verdict[i] (n bytes):
+ *   0  the half is the DAH's;
+ *   2  nmt would refuse a push of the completed vector, because a namespace
+ *      is below the one before it (checked first: a root over such a vector
+ *      cannot come from an honest tree, whatever it is);
+ *   1  the root differs.
+ * vectors (n*2k*512 bytes, may be NULL): every completed vector, whatever its
+ * verdict, in the caller's order.  k a power of two <= 1024, else
+ * CDA_ERR_INVALID, "square width must be a power of two <= 1024".  One
+ * synchronisation. */
+int cda_square_axis_halves(cda_square *sq, const uint8_t *axes, const uint32_t *indexes, const uint8_t *sides,
+                           uint32_t n, uint8_t *shares);
+int cda_square_set_axis_halves(cda_square_set *set, const uint32_t *squares, const uint8_t *axes,
+                               const uint32_t *indexes, const uint8_t *sides, uint32_t n, uint8_t *shares);
+int cda_axis_halves_verify(cda_ctx *ctx, uint32_t k, const uint8_t *row_roots, const uint8_t *col_roots,
+                           uint32_t n_squares, const uint32_t *squares, const uint8_t *axes, const uint32_t *indexes,
+                           const uint8_t *sides, uint32_t n, const uint8_t *shares, uint8_t *verdict,
+                           uint8_t *vectors);
+/* The mirror of cda_rs_encode: the n_shards data shards of every codeword from
+ * its n_shards parity shards alone (parity, data: n_codewords * n_shards *
+ * shard_len bytes, codeword by codeword).  Leopard's encode is two invertible
+ * transforms; this runs their inverses on the encoder's own kernels, without
+ * the general decoder's error locator.  n_shards a power of two <= 1024, else
+ * CDA_ERR_UNSUPPORTED; shard_len a multiple of 64, else CDA_ERR_CHUNK_SIZE
+ * with cda_rs_encode's text. */
+int cda_rs_recover_data(cda_ctx *ctx, const uint8_t *parity, uint32_t n_shards, uint32_t shard_len,
+                        uint32_t n_codewords, uint8_t *data);
 
 /* ---- Standalone erasured NMT trees -----------
  * wrapper.NewErasuredNamespacedMerkleTree(squareSize, axisIndex), n_cells
